@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: gossip node-rounds/s on the SCALE engine (BASELINE.json configs 3-5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-pview] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-pview] [--no-cpu-baseline]
+
+A plain run measures the headline alone and prints its line; --full adds everything below that
+is not the headline's own run (the detection latencies read from its records, `events_off`, the
+CPU baselines, `pview*`, `full262k`, `full_rows`).  --dump-outputs DIR writes what the last
+timed tick left (digest, a seeded sample of table rows, the peers chosen) as DIR/<name>.npy;
+the workload is seeded, so two builds run with the same arguments compare array for array.
 
 One "step" = one protocol tick over the whole node population: every alive node merges
 the rows gossiped to it, bumps its heartbeat, runs the TREMOVE scan and gossips to `fanout`
@@ -399,11 +406,44 @@ def tiles_for(nodes, world):
     return total // world
 
 
-def run_full(nodes, steps, warmup, world, local, dist, layout="columns", events=False, tiles=None):
+DUMP_ROWS = 64               # table rows --dump-outputs samples (seeded by SEED)
+DUMP_BYTES = 60 << 20        # ... fewer when the float32 rows and the peers would pass this
+
+
+def dump_outputs(eng, nodes, last_tick, path):
+    """--dump-outputs: what the timed path left after its last tick, as a caller reads it back
+    through the engine, one .npy each (float32 / float64, every value exactly representable):
+      digest        the last tick's digest: tick, node_rounds, merges, sent, dropped, delivered,
+                    joins, removes, then event_hash as its high and low 32 bits
+      row_ids       a fixed sample of table rows (row 0, the last row, the rest drawn from SEED)
+      rows          the packed entries of those rows (hb << 5 | ts mod 32, 0 = absent;
+                    scale.unpack), len(row_ids) x nodes
+      messages      the peers every node chose in the last tick (-1: none), nodes x fanout
+    """
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    d = eng.digest(last_tick)
+    h = d.pop("event_hash")
+    np.save(os.path.join(path, "digest.npy"),
+            np.array([d[k] for k in ("tick", "node_rounds", "merges", "sent", "dropped",
+                                     "delivered", "joins", "removes")] + [h >> 32, h & 0xFFFFFFFF],
+                     np.float64))
+    k = max(2, min(DUMP_ROWS, nodes, (DUMP_BYTES - 8 * nodes * eng.fanout) // (4 * nodes)))
+    rng = np.random.default_rng(SEED)
+    ids = np.unique(np.concatenate([[0, nodes - 1], rng.integers(0, nodes, k - 2)]))
+    np.save(os.path.join(path, "row_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(path, "rows.npy"),
+            np.stack([eng.row(int(r)) for r in ids]).astype(np.float32))
+    np.save(os.path.join(path, "messages.npy"), eng.messages().astype(np.float64))
+
+
+def run_full(nodes, steps, warmup, world, local, dist, layout="columns", events=False, tiles=None,
+             event_stats=True, dump=None):
     """Full-view workload (config 3 rules) on `world` GPUs: one GPU fused, or column / row
     shards.  Returns job totals (time and kernel time are the slowest rank's).  events: the
     tick kernels also append every join / remove record to the device ring (drained after
-    the timed region; event_summary)."""
+    the timed region; event_summary, unless event_stats is off).  dump: a directory for
+    dump_outputs (one GPU)."""
     import torch
     from gossip_protocol_amd.scale import FAIL_RANDOM, ScaleEngine
     kw = dict(fanout=FANOUT, fail_mode=FAIL_RANDOM, fail_tick=FAIL_TICK, fail_ppm=FAIL_PPM,
@@ -449,10 +489,12 @@ def run_full(nodes, steps, warmup, world, local, dist, layout="columns", events=
     kern_ms = (perf1["merge_ms"] - perf0["merge_ms"]) / launches
     csr_ms = (perf1["csr_ms"] - perf0["csr_ms"]) / launches
     ev = None
-    if events:
+    if events and event_stats:
         from gossip_protocol_amd import _lib
         ev = event_summary(eng, nodes, warmup + steps, dist,
                            _lib.fail_schedule(nodes, SEED, FAIL_RANDOM, FAIL_TICK, FAIL_PPM))
+    if dump:
+        dump_outputs(eng, nodes, warmup + steps, dump)
     eng.close()
     if dist is not None:
         # per-row counts live on rank 0 only (columns) or on the row's owner (rows): the sum is
@@ -600,9 +642,18 @@ def main(argv=None):
                     help="skip the SWIM + TFAIL config-5 line item")
     ap.add_argument("--no-inbox7", action="store_true",
                     help="skip the bounded-inbox config-5 line item (inbox 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: the failure-detection summary of "
+                         "its event records, the CPU baselines and the secondary line items "
+                         "(the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline's last timed tick left (dump_outputs) as "
+                         "DIR/<name>.npy; one GPU")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and world > 1:
+        ap.error("--dump-outputs reads the table back from one engine: run it with one GPU")
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     import torch
@@ -614,13 +665,21 @@ def main(argv=None):
             dist.init_process_group("nccl")
     # the headline records every join / remove on the device (the reference's Log lines)
     full = run_full(args.nodes, args.steps, args.warmup, world, local, dist,
-                    events=not args.no_events)
+                    events=not args.no_events, event_stats=args.full, dump=args.dump_outputs)
     out = None
     if rank == 0:
         out = summarize_full(full, args.nodes, args.steps, world, args.warmup)
         out["event_stream"] = "on" if not args.no_events else "off"
         out.update({"n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                     "higher_is_better": True, "vs_baseline": None})
+    if not args.full:
+        # a plain run is the headline alone: set up, warm up, time the steps, print the line
+        if out is not None:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             # the reference itself (N = 10, the only size it runs), with our restatement of
             # the config-3 protocol beside it (scaled to 65,536-wide rows)

@@ -23,7 +23,7 @@ for s in "$@"; do
         tests) step tests 1100 python -u -m pytest $R/tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
         tests:*) step tests_k 600 python -u -m pytest $R/tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${s#tests:}" ;;
         smoke) step smoke 200 python -u -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; g.smoke()" ;;
-        bench) step bench 600 python -u $R/bench.py ;;
+        bench) step bench 600 python -u $R/bench.py --full ;;
         bench5) step bench5 300 python -u $R/scripts/bench_pview.py --steps 20 --warmup 5 --no-cpu-baseline ;;
         trace3) step trace3 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace3" -o run --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pview --no-262k --no-events ;;
         trace5) step trace5 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace5" -o run --output-format csv -- python3 $R/scripts/bench_pview.py --steps 20 --warmup 5 --no-cpu-baseline ;;

@@ -10,7 +10,7 @@ rc=$?
 tail -3 "$OUT/gpu_tests.log"
 [ $rc -ne 0 ] && exit $rc
 if [ "$2" = bench ]; then
-    timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout -k 10 600 python -u bench.py --full >"$OUT/bench.json" 2> "$OUT/bench.err"
     rc=$?
     tail -c 600 "$OUT/bench.json"
     exit $rc

@@ -85,7 +85,7 @@ def _worker(rank, world, port, q):
     import bench
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--steps", str(N_STEPS), "--warmup", str(N_WARM), "--nodes", "1024",
+        bench.main(["--full", "--steps", str(N_STEPS), "--warmup", str(N_WARM), "--nodes", "1024",
                     "--pview-nodes", "4096", "--no-cpu-baseline"])
     q.put((rank, buf.getvalue()))
 
@@ -157,7 +157,72 @@ def test_bench_two_ranks_gloo():
     assert ps["removes_of_live_frac"] == 0.0 and ps["crashed_nodes_detected"] == 2
 
 
-INBOXES_WITH_PMC = [0, 7]       # committed profiles/pmc_*_pview*.json (0: drain all, 7: inbox 7)
+class FakeTable(FakeEngine):
+    """A one-GPU stand-in with a readable table: entry (r, c) = (r + c) mod 65536 after any
+    tick, no peers chosen; records may be drained after the warm-up only."""
+    fanout = 3
+
+    def digest(self, t):
+        return dict(super().digest(t), sent=7, dropped=1, joins=2, removes=3,
+                    event_hash=0xDEADBEEFCAFEF00D)
+
+    def drain_events(self):
+        assert self.t == N_WARM, "a plain run reads no records after the timed ticks"
+        return super().drain_events()
+
+    def layout(self):
+        return (1, 0, self.n)
+
+    def row(self, r):
+        import numpy as np
+        return (np.arange(self.n) + r).astype(np.uint16)
+
+    def messages(self):
+        import numpy as np
+        return np.full((self.n, self.fanout), -1, np.int32)
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path, monkeypatch, capsys):
+    """Without --full: one engine, warmup + steps ticks, one line with the headline's fields and
+    none of the other items; --dump-outputs writes the last tick's digest, the sampled rows and
+    the peers as float arrays, the same from run to run."""
+    import numpy as np
+    import gossip_protocol_amd.scale as scale
+    import bench
+    made = []
+
+    def engine(n, **kw):
+        made.append(FakeTable(n, 0, 1))
+        return made[-1]
+    monkeypatch.setattr(scale, "ScaleEngine", engine)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    n = 1024
+    for d in ("a", "b"):
+        bench.main(["--steps", str(N_STEPS), "--warmup", str(N_WARM), "--nodes", str(n),
+                    "--dump-outputs", str(tmp_path / d)])
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 2 and len(made) == 2 and made[0].t == N_WARM + N_STEPS
+    out = json.loads(lines[0])
+    assert out["steps"] == N_STEPS and out["unit"] == "node-rounds/s" and out["dtype"] == "u16"
+    assert out["higher_is_better"] is True and out["ms_per_step"] > 0 and out["event_stream"] == "on"
+    assert abs(out["value"] - n * N_STEPS / (out["ms_per_step"] * N_STEPS / 1e3)) < 1e-6 * out["value"]
+    assert not {"events", "events_off", "cpu_baseline", "pview", "pview_swim", "pview_inbox7",
+                "full262k", "full_rows"} & set(out)
+    a = {f: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(a) == ["digest.npy", "messages.npy", "row_ids.npy", "rows.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["digest.npy"].tolist() == [N_WARM + N_STEPS, n, 3 * n, 7, 1, 2 * n, 2, 3,
+                                        0xDEADBEEF, 0xCAFEF00D]
+    ids = a["row_ids.npy"].astype(np.int64)
+    assert ids[0] == 0 and ids[-1] == n - 1 and len(set(ids.tolist())) == len(ids) > 2
+    assert np.array_equal(a["rows.npy"], (np.arange(n)[None, :] + ids[:, None]).astype(np.float32))
+    assert a["messages.npy"].shape == (n, 3) and np.all(a["messages.npy"] == -1)
+    for f, v in a.items():
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / f))), f
+
+
+INBOXES_WITH_PMC = [0, 7]      # committed profiles/pmc_*_pview*.json (0: drain all, 7: inbox 7)
 
 
 def test_counter_fields_only_for_their_window():

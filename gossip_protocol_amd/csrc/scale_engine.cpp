@@ -37,8 +37,11 @@ struct Shard {
     gsp::DevBuf<uint16_t> table[2];
     gsp::DevBuf<int32_t> own_hb, fail_tick, cnt_total[2], cnt_slice, cnt_all, out_dst, picks,
         ping, deg, off, fill, csr_src, err, tile_sum, start_tick, joiners, join_ok,
-        long_list;                 // [2][1 + rows] by tick parity: rows with k > kMaxSegment
+        long_list,                 // [2][1 + rows] by tick parity: rows with k > kMaxSegment
                                    // (a CSR owner's: shard 0 of a shared group, else each)
+        mid_list,                  // sub-slab sweep: the same for kSweepMaxSeg < k <= kMaxSegment
+        cnt_sub;                   // sub-slab sweep: [local tiles][stride / W][n] on shard 0 of a
+                                   // shared group, else [stride / W][n] on each shard
     gsp::DevBuf<uint16_t> intro_buf;   // row layout, shards != 0: node 0's row of the last tick
     gsp::DevBuf<uint8_t> bitmap;
     gsp::DevBuf<unsigned long long> dig;
@@ -47,7 +50,7 @@ struct Shard {
     void release() {
         for (int b = 0; b < 2; ++b) { table[b].release(); cnt_total[b].release(); }
         for (auto *x : {&own_hb, &fail_tick, &cnt_slice, &cnt_all, &out_dst, &picks, &ping, &deg, &off,
-                        &fill, &csr_src, &err, &tile_sum, &start_tick, &joiners, &join_ok, &long_list})
+                        &fill, &csr_src, &err, &tile_sum, &start_tick, &joiners, &join_ok, &long_list, &mid_list, &cnt_sub})
             x->release();
         intro_buf.release();
         bitmap.release();
@@ -84,6 +87,9 @@ struct gsp_scale {
     int policy = 5;            // bit 0 nt own row, bit 1 nt sender rows, bit 2 pipelined loads
     int merge = 1;             // 1 packed 16-bit merge, 0 per-entry form
     int32_t lds_pad = 0;       // GSP_TEST_SCALE_LDS_PAD: extra LDS per tick-kernel workgroup
+    int32_t sweep = 0;         // sub-slab width of the tile sweep (scale_sweep_kernel), 0: off;
+                               // fixed at create (sweep_width below, GSP_TEST_SCALE_SWEEP)
+    int32_t sweep_seg = gsp::kSweepMaxSeg;   // the sweep defers rows with more messages
     std::vector<Shard> local;  // shards held by this engine (1, or G for an in-process group)
     gsp::DevBuf<gsp::ScaleTickArgs> long_tpl;   // [local][2]: every tile's args by tick parity
                                                 // (scale_long_kernel)
@@ -160,6 +166,13 @@ struct gsp_scale {
         a.ev = sh.ev.args();
         // the rows this tile's CSR defers (k > kMaxSegment): appended by the CSR's owner only
         a.long_list = &sh == &owner(sh) ? long_list(sh, t) : nullptr;
+        if (sweep && merge == 1) {
+            a.sweep = sweep;
+            a.sweep_seg = sweep_seg;
+            const size_t per = size_t(stride / sweep) * size_t(p.n);
+            a.cnt_sub = shared ? s0.cnt_sub.p + size_t(sh.g - rank) * per : sh.cnt_sub.p;
+            a.mid_list = &sh == &owner(sh) ? mid_list(sh, t) : nullptr;
+        }
         return a;
     }
 
@@ -168,6 +181,11 @@ struct gsp_scale {
     int32_t *long_list(const Shard &sh, int32_t t) const {
         const Shard &o = owner(sh);
         return o.long_list.p + size_t(t & 1) * size_t(1 + o.rows);
+    }
+
+    int32_t *mid_list(const Shard &sh, int32_t t) const {
+        const Shard &o = owner(sh);
+        return o.mid_list.p ? o.mid_list.p + size_t(t & 1) * size_t(1 + o.rows) : nullptr;
     }
 
     gsp::ScaleResolveArgs resolve_args(Shard &sh, int32_t t) const {
@@ -262,7 +280,13 @@ int shard_alloc(gsp_scale *s, Shard &sh) {
     if (!s->shared || &sh == &s->local[0]) {
         GSP_HIP(sh.long_list.alloc(2 * (rows + 1)));
         GSP_HIP(hipMemsetAsync(sh.long_list.p, 0, 2 * (rows + 1) * 4, st));
+        if (s->sweep) {
+            GSP_HIP(sh.mid_list.alloc(2 * (rows + 1)));
+            GSP_HIP(hipMemsetAsync(sh.mid_list.p, 0, 2 * (rows + 1) * 4, st));
+        }
     }
+    if (s->sweep && (!s->shared || &sh == &s->local[0]))
+        GSP_HIP(sh.cnt_sub.alloc(size_t(s->stride / s->sweep) * size_t(n) * (s->shared ? s->local.size() : 1)));
     if (s->sliced && (!s->shared || &sh == &s->local[0])) {
         GSP_HIP(sh.cnt_slice.alloc(size_t(n)));
         GSP_HIP(sh.cnt_all.alloc(size_t(n) * s->shards * (s->shared ? 2 : 1)));
@@ -534,6 +558,7 @@ int upload_long_tpl(gsp_scale *s) {
             gsp::ScaleTickArgs x = s->args(sh, 2 + par);
             x.dig = sh.dig.p;
             x.long_list = s->long_list(sh, par);
+            x.mid_list = s->mid_list(sh, par);
             tpl.push_back(x);
         }
     if (!s->long_tpl.p) GSP_HIP(s->long_tpl.alloc(tpl.size()));
@@ -541,6 +566,27 @@ int upload_long_tpl(gsp_scale *s) {
     GSP_HIP(hipMemcpy(s->long_tpl.p, tpl.data(), tpl.size() * sizeof(gsp::ScaleTickArgs),
                       hipMemcpyHostToDevice));
     return GSP_OK;
+}
+
+// The sub-slab width of the tile sweep, or 0 for the workgroup-per-row kernel.  The sweep takes
+// the slice form of the plain protocol only (no TFAIL, SWIM, join schedule or test bound on the
+// segments), and by default only where a sub-slab of both tables, 2 * rows * W * 2 B, stays
+// resident in the 256 MiB Infinity Cache with margin (DESIGN.md "Column tiles").
+// GSP_TEST_SCALE_SWEEP=0|512 (tests, A/B) overrides the default and the residency rule (any
+// other width selects the workgroup-per-row kernel); 512:K also lowers the messages a row may
+// have before it is deferred to K (tests: the plain protocol makes no row with more than
+// kSweepMaxSeg).
+int32_t sweep_width(gsp_scale &s) {
+    if (!s.sliced || s.p.tfail > 0 || s.p.swim > 0 || s.joins || s.max_segment != INT32_MAX) return 0;
+    int32_t w = gsp::kSweepWidth;
+    if (int64_t(s.p.n) * w * 4 > (int64_t(160) << 20)) w = 0;
+    if (const char *e = std::getenv("GSP_TEST_SCALE_SWEEP")) {
+        w = std::atoi(e);
+        if (const char *c = std::strchr(e, ':'))
+            s.sweep_seg = std::max(1, std::min<int32_t>(gsp::kSweepMaxSeg, std::atoi(c + 1)));
+    }
+    if (w != gsp::kSweepWidth) w = 0;
+    return w;
 }
 
 int scale_build(const gsp_scale_params *p, int device, int32_t shards, int32_t rank,
@@ -605,6 +651,7 @@ int scale_build(const gsp_scale_params *p, int device, int32_t shards, int32_t r
     }
     if (const char *ms = std::getenv("GSP_TEST_MAX_SEGMENT"))   // tests only: force overflows
         s->max_segment = std::max(1, std::atoi(ms));
+    s->sweep = sweep_width(*s);
     GSP_HIP(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
     GSP_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_err), size_t(local_shards) * 4));
     std::memset(s->h_err, 0, size_t(local_shards) * 4);
@@ -748,6 +795,10 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
         for (Shard &sh : s->local)
             GSP_HIP(gsp::launch_scale_tick(s->args(sh, t), s->sliced, s->merge, s->st));
+        if (s->sweep && s->merge == 1) {      // the sweep's per-sub-slab member counts -> cnt_cur
+            if (s->shared) GSP_HIP(gsp::launch_sweep_counts(s->args(s->local[0], t), int32_t(s->local.size()), s->st));
+            else for (Shard &sh : s->local) GSP_HIP(gsp::launch_sweep_counts(s->args(sh, t), 1, s->st));
+        }
         // the rows with more than kMaxSegment messages the launches above deferred (usually
         // none: one short launch per tick)
         GSP_HIP(gsp::launch_scale_long(s->args(s->local[0], t), s->long_tpl.p, int32_t(s->local.size()),

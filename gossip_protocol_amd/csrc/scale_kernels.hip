@@ -12,6 +12,9 @@
 // One 256-lane workgroup per row streams the row in 2048-column chunks: it reads its own
 // row and each sender's row once (16 B per lane, fully coalesced) and writes its row once,
 // so the kernel is HBM-bound at (2 + k) * stride * 2 bytes per row with k messages.
+// scale_sweep_kernel runs the same tick of a column tile of the plain protocol one wave per
+// (row, 512-column sub-slab), sub-slab by sub-slab, so that the sender re-reads of the previous
+// table are served by the Infinity Cache.
 #include "join_kernels.hpp"
 #include "philox.hpp"
 #include "scale_kernels.hpp"
@@ -802,6 +805,253 @@ __global__ void __launch_bounds__(kScaleBlock) scale_tick_kernel(ScaleTickArgs a
     scale_tick_row<kInit, kSlice, kMerge, kPolicy, kPipe, kTfail, kSwim, false>(a, int32_t(blockIdx.x));
 }
 
+// The sub-slab sweep of a column tile (slice form, plain protocol; DESIGN.md "Column tiles"):
+// the tile's stride columns are cut into stride / W sub-slabs of W = 512 * kV columns and the
+// grid walks them sub-slab-major (blockIdx = sub-slab * batches + batch), so that between two
+// reads of a previous-table line the chip touches one sub-slab of prev and one of cur, which
+// the Infinity Cache holds.  A work item is one wave on (row, sub-slab): a workgroup takes
+// kSweepBatch consecutive rows of one sub-slab, 16 per wave, with no barrier and no LDS on
+// the row path (LDS stages event records only).
+//   prologue  lane i of a wave loads row i's CSR bounds and crash tick, and the wave loads the
+//             16 rows' (contiguous) sender ids in one request; rows are walked by readlane
+//   order     ascending sender, ranked in registers (one id per lane, k <= sweep_seg <= kSweepMaxSeg)
+//   deferred  rows with more messages go to mid_list (k <= kMaxSegment) or long_list, appended
+//             by the sub-slab-0 item of the CSR's owner; scale_long_kernel runs them
+//   results   the presence byte per lane as in the block form; the slice member count as one
+//             plain store per (sub-slab, row) to cnt_sub, summed by sweep_count_kernel; digest
+//             sums kept in registers over the wave's rows and added once, when non-zero; the
+//             per-row quantities (rounds, merges, delivered, own_hb) by the sub-slab-0 item
+// 5 waves per SIMD (96 VGPRs, 10 dwords of scratch for values the row loop does not touch):
+// measured at config 3 against 4 waves (107 VGPRs, no scratch) and 6 (80 VGPRs, 26 dwords):
+// 6.21 ms per tick against 7.07 and 6.97 (DESIGN.md "Column tiles").
+template <bool kNtCur>
+__global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_eu(5, 8))) scale_sweep_kernel(ScaleTickArgs a) {
+    constexpr int W = kSweepWidth;
+    const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t batches = (a.rows + kSweepBatch - 1) / kSweepBatch;
+    const int32_t sub = int32_t(blockIdx.x) / batches, batch = int32_t(blockIdx.x) - sub * batches;
+    if (*a.err) return;
+    const int32_t t = a.tick;
+    const int32_t lr0 = batch * kSweepBatch + wave * (kSweepBatch / 4);
+    if (lr0 >= a.rows) return;
+    const int64_t stride = a.stride;
+    const uint32_t t5 = uint32_t(t) & 31u, tr = uint32_t(a.tremove);
+    const PackedConsts pc = packed_consts(t5, tr);
+
+    // batch prologue: lane i holds row lr0 + i (m_k = -1: crashed, or past the last row)
+    const int32_t mlr = lr0 + (lane & 15);
+    int32_t m_off = 0, m_k = -1;
+    if (lane < kSweepBatch / 4 && mlr < a.rows) {
+        m_off = a.off[mlr];
+        if (t <= a.fail_tick[a.row0 + mlr]) m_k = a.off[mlr + 1] - m_off;
+    }
+    const int32_t nrows = a.rows - lr0 < kSweepBatch / 4 ? a.rows - lr0 : kSweepBatch / 4;
+    const int32_t seg0 = int32_t(lane_of(uint32_t(m_off), 0));
+    const int32_t seg1 = a.off[lr0 + nrows];
+    const int32_t seg = seg0 + lane < seg1 ? a.csr_src[seg0 + lane] : 0;   // the first 64 senders
+
+    uint32_t *const s_ev = s_bits + wave * W;
+    unsigned long long *const ev_buf = a.ev.buf ? ev_stripe_buf(a.ev) : nullptr;
+    unsigned long long *const ev_count = ev_stripe_count(a.ev);
+    uint32_t joins = 0, removes = 0, delivered = 0, m_cnt = 0;
+    uint64_t hsum = 0, merges = 0;
+
+    const int64_t lc0 = int64_t(sub) * W + lane * kEntriesPerLane;     // column in this table
+    const int64_t gc0 = a.col0 + lc0;                                   // global column
+    // the next row the wave runs, from row i on (nrows: none); a row with more messages than
+    // the wave orders is deferred on the way
+    auto next_row = [&](int32_t i) {
+        for (; i < nrows; ++i) {
+            const int32_t k = int32_t(lane_of(uint32_t(m_k), i));
+            if (k < 0) continue;
+            if (k <= a.sweep_seg) break;
+            int32_t *const list = k > kMaxSegment ? a.long_list : a.mid_list;
+            if (sub == 0 && lane == 0 && list) list[1 + atomicAdd(&list[0], 1)] = lr0 + i;
+        }
+        return i;
+    };
+    // row i's senders in ascending order, one per lane (ids are distinct), and the request of
+    // its own vector and its first 4 senders' vectors (16 B per lane each)
+    auto request = [&](int32_t i, int32_t &k, int32_t &sorted, uint4 &e, uint4 (&sv)[4]) {
+        k = int32_t(lane_of(uint32_t(m_k), i));
+        const int32_t o0 = int32_t(lane_of(uint32_t(m_off), i));
+        int32_t sid;
+        if (o0 - seg0 + k <= 64) sid = __builtin_amdgcn_ds_bpermute((o0 - seg0 + lane) << 2, seg);
+        else sid = lane < k ? a.csr_src[o0 + lane] : 0;
+        if (lane >= k) sid = INT32_MAX;
+        int32_t rk = 0;
+        for (int32_t j = 0; j < k; ++j) rk += int32_t(lane_of(uint32_t(sid), j)) < sid ? 1 : 0;
+        sorted = __builtin_amdgcn_ds_permute((lane < k ? rk : lane) << 2, sid);
+        if (sub == 0 && a.count_rounds) {
+            if (lane < k) merges += 1ull + uint64_t(a.cnt_prev[sid]);
+            delivered += lane == 0 ? uint32_t(k) : 0u;
+        }
+        e = ld16<false>(a.prev + int64_t(lr0 + i) * stride + lc0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (u < k)
+                sv[u] = ld16<false>(a.prev + int64_t(int32_t(lane_of(uint32_t(sorted), u)) - a.row0) * stride + lc0);
+    };
+
+    // the rows are pipelined: row i + 1's vectors are requested before row i is merged
+    int32_t k = 0, sorted = 0, nk = 0, nsorted = 0;
+    uint4 e = make_uint4(0u, 0u, 0u, 0u), ne = e, sv[4], nsv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) sv[u] = nsv[u] = e;
+    int32_t i = next_row(0);
+    if (i < nrows) request(i, k, sorted, e, sv);
+    while (i < nrows) {
+        const int32_t lr = lr0 + i, r = a.row0 + lr;
+        const int32_t ni = next_row(i + 1);
+        if (ni < nrows) request(ni, nk, nsorted, ne, nsv);
+        uint16_t *own_cur = a.cur + int64_t(lr) * stride;
+        uint32_t live = 0, ev_fill = 0;
+        {
+            const uint32_t w0[4] = {e.x, e.y, e.z, e.w};
+            for (int32_t j0 = 0; j0 < k; j0 += 4) {
+                int32_t ss[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (j0 + u < k) {
+                        ss[u] = int32_t(lane_of(uint32_t(sorted), j0 + u));
+                        if (j0) sv[u] = ld16<false>(a.prev + int64_t(ss[u] - a.row0) * stride + lc0);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (j0 + u >= k) break;
+                    e.x = merge_word_packed(e.x, sv[u].x, pc);
+                    e.y = merge_word_packed(e.y, sv[u].y, pc);
+                    e.z = merge_word_packed(e.z, sv[u].z, pc);
+                    e.w = merge_word_packed(e.w, sv[u].w, pc);
+                    // the sender's own entry: hb + 1 and ts = now, or add (1, now)
+                    const int64_t ds = int64_t(ss[u]) - gc0;
+                    if (ds >= 0 && ds < kEntriesPerLane)
+                        patch16(e, int(ds), [t5](uint32_t old) { return (((old >> 5) + 1u) << 5) | t5; });
+                }
+            }
+            const int64_t dr = int64_t(r) - gc0;      // never list yourself
+            if (dr >= 0 && dr < kEntriesPerLane) patch16(e, int(dr), [](uint32_t) { return 0u; });
+            uint32_t ws[4] = {e.x, e.y, e.z, e.w};
+
+            // TREMOVE scan, events and presence bits of the 8 entries (as the block form)
+            uint32_t ev = 0, bits = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t pe = pk_min(ws[q], pc.one);
+                const uint32_t age = (pc.t32 - (ws[q] & pc.low5)) & pc.low5;
+                ev |= pk_min(pk_subc(age, pc.trm1), pe);          // present and stale
+                ev |= pk_subc(pe, pk_min(w0[q], pc.one));          // absent before, present now
+                bits |= ((pe | (pe >> 15)) & 3u) << (2 * q);
+            }
+            uint32_t evj = 0, evr = 0;
+            if (ev != 0) {
+                bits = 0;
+#pragma unroll
+                for (int q = 0; q < kEntriesPerLane; ++q) {
+                    const int sh = (q & 1) * 16;
+                    uint32_t ent = (ws[q >> 1] >> sh) & 0xFFFFu;
+                    if (ent) {
+                        const uint32_t before = (w0[q >> 1] >> sh) & 0xFFFFu;
+                        if (((t5 - ent) & 31u) >= tr) {     // TREMOVE scan (MP1Node.cpp:340)
+                            removes++;
+                            hsum += event_mix(2, uint32_t(t), uint32_t(r), uint32_t(gc0 + q));
+                            ws[q >> 1] &= ~(0xFFFFu << sh);
+                            ent = 0;
+                            evr |= 1u << q;
+                        } else if (!before) {
+                            joins++;
+                            hsum += event_mix(1, uint32_t(t), uint32_t(r), uint32_t(gc0 + q));
+                            evj |= 1u << q;
+                        }
+                    }
+                    bits |= (ent ? 1u : 0u) << q;
+                }
+            }
+            if (ev_buf) {                         // the event stream: stage this vector's records
+                uint32_t both = ((a.ev.kinds & GSP_EVENTS_JOIN) ? evj : 0u) |
+                                ((a.ev.kinds & GSP_EVENTS_REMOVE) ? (evr << 8) : 0u);
+                const uint32_t cnt = uint32_t(__builtin_popcount(both));
+                if (__ballot(cnt > 0)) {          // wave-uniform
+                    const uint32_t incl = wave_incl_scan(cnt);
+                    uint32_t p = ev_fill + incl - cnt;
+                    while (both) {
+                        const uint32_t b = uint32_t(__builtin_ffs(both) - 1);
+                        both &= both - 1;
+                        s_ev[p++] = ((b < 8 ? 1u : 2u) << 30) | uint32_t(gc0 + (b & 7u));
+                    }
+                    ev_fill += lane_of(incl, 63);
+                }
+            }
+            live += __builtin_popcount(bits);
+            st16<kNtCur>(own_cur + lc0, ws);
+            a.bitmap[int64_t(lr) * (stride >> 3) + (lc0 >> 3)] = uint8_t(bits);
+        }
+        const uint32_t row_live = wave_sum32(live);
+        if (lane == i) m_cnt = row_live;
+        if (ev_fill) {                            // the item's one ring reservation
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(ev_count, (unsigned long long)ev_fill);
+            base = (uint64_t(lane_of(uint32_t(base >> 32), 0)) << 32) | lane_of(uint32_t(base), 0);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t q = uint32_t(lane); q < ev_fill; q += 64) {
+                const uint32_t s = s_ev[q];
+                if (int64_t(base + q) < a.ev.cap)
+                    ev_buf[base + q] = event_record(s >> 30, uint32_t(t), uint32_t(r), s & 0x3FFFFFFFu);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        i = ni;
+        k = nk;
+        sorted = nsorted;
+        e = ne;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sv[u] = nsv[u];
+    }
+
+    // the batch's results: counts by the lanes that hold the rows, the digest once per wave
+    const bool ran = lane < kSweepBatch / 4 && m_k >= 0 && m_k <= a.sweep_seg;
+    if (ran) {
+        a.cnt_sub[int64_t(sub) * a.n + a.row0 + mlr] = int32_t(m_cnt);
+        if (sub == 0) a.own_hb[mlr] += 1;
+    }
+    unsigned long long *dig = a.dig + (blockIdx.x % kDigSlots) * kDigFields;
+    const uint32_t tj = wave_sum32(joins), trm = wave_sum32(removes);
+    const uint64_t th = wave_sum64(hsum);
+    if (lane == 0) {
+        if (tj) atomicAdd(&dig[kDigJoins], (unsigned long long)tj);
+        if (trm) atomicAdd(&dig[kDigRemoves], (unsigned long long)trm);
+        if (th) atomicAdd(&dig[kDigHash], (unsigned long long)th);
+    }
+    if (sub == 0 && a.count_rounds) {
+        const uint32_t rounds = uint32_t(__builtin_popcountll(__ballot(ran)));
+        const uint64_t tm = wave_sum64(merges);
+        const uint32_t td = wave_sum32(delivered);
+        if (lane == 0 && rounds) {
+            atomicAdd(&dig[kDigRounds], (unsigned long long)rounds);
+            atomicAdd(&dig[kDigMerges], (unsigned long long)tm);
+            atomicAdd(&dig[kDigDelivered], (unsigned long long)td);
+        }
+    }
+}
+
+// cnt_cur[r] of every tile of the launch (blockIdx.y) = the sum of the sweep's per-sub-slab
+// counts, for the rows the sweep ran: a crashed row keeps its count and a deferred row's is
+// written by its own workgroup (scale_long_kernel).
+__global__ void __launch_bounds__(256) sweep_count_kernel(ScaleTickArgs a, int32_t subs) {
+    if (*a.err) return;
+    const int32_t lr = int32_t(blockIdx.x) * 256 + int32_t(threadIdx.x);
+    if (lr >= a.rows) return;
+    const int32_t r = a.row0 + lr;
+    if (a.tick > a.fail_tick[r] || a.off[lr + 1] - a.off[lr] > a.sweep_seg) return;
+    const int32_t *sub = a.cnt_sub + int64_t(blockIdx.y) * subs * a.n + r;
+    int32_t sum = 0;
+    for (int32_t s = 0; s < subs; ++s) sum += sub[int64_t(s) * a.n];
+    a.cnt_cur[int64_t(blockIdx.y) * a.n + r] = sum;
+}
+
 // The rows the tick kernels deferred (k > kMaxSegment), after every tick-kernel launch of the
 // tick: tile g's args are its template of this tick's parity (made by the host, upload_long_tpl
 // in scale_engine.cpp) with the tick's own fields patched below -- tick, drop_pct, drop_prev,
@@ -823,9 +1073,21 @@ __global__ void __launch_bounds__(kScaleBlock) scale_long_kernel(ScaleTickArgs a
             scale_tick_row<false, kSlice, 1, 0, false, kTfail, kSwim, true>(ag, ag.long_list[1 + i]);
             __syncthreads();                    // the row's LDS is read to its end
         }
+        // the rows the sub-slab sweep left to the block form (kSweepMaxSeg < k <= kMaxSegment)
+        if constexpr (kSlice && !kTfail && !kSwim) {
+            const int32_t mid = ag.mid_list ? ag.mid_list[0] : 0;
+            for (int32_t i = int32_t(blockIdx.x); i < mid; i += int32_t(gridDim.x)) {
+                scale_tick_row<false, true, 1, 0, false, false, false, false>(ag, ag.mid_list[1 + i]);
+                __syncthreads();
+            }
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int32_t g = 0; g < ntiles; ++g) tpl[2 * g + ((t + 1) & 1)].long_list[0] = 0;
+        for (int32_t g = 0; g < ntiles; ++g) {
+            const ScaleTickArgs &nx = tpl[2 * g + ((t + 1) & 1)];
+            nx.long_list[0] = 0;
+            if (nx.mid_list) nx.mid_list[0] = 0;
+        }
 }
 
 // Column mode: one wave per sender.  The global member order of row s is the shards'
@@ -1063,8 +1325,30 @@ void launch_tick_policy(const ScaleTickArgs &a, int policy, size_t lds, hipStrea
     }
 }
 
+// one launch of the sub-slab sweep over a tile (a.sweep = W); nt_own: non-temporal stores of cur
+hipError_t launch_scale_sweep(const ScaleTickArgs &a, hipStream_t st) {
+    const int32_t W = a.sweep;
+    if (W != kSweepWidth || a.stride % W || a.sweep_seg < 1 || a.sweep_seg > kSweepMaxSeg || !a.cnt_sub || !a.bitmap || a.csr_slot ||
+        a.tfail > 0 || a.swim > 0 || a.start_tick)
+        return hipErrorInvalidValue;
+    const int64_t blocks = (a.stride / W) * ((int64_t(a.rows) + kSweepBatch - 1) / kSweepBatch);
+    const dim3 grid{unsigned(blocks)}, block(kScaleBlock);
+    const size_t lds = a.ev.buf ? size_t(4) * size_t(W) * 4 : 0;
+    if (a.nt_own) hipLaunchKernelGGL((scale_sweep_kernel<true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((scale_sweep_kernel<false>), grid, block, lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sweep_counts(const ScaleTickArgs &a, int32_t tiles, hipStream_t st) {
+    if (a.sweep != kSweepWidth || tiles < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sweep_count_kernel, dim3(unsigned((a.rows + 255) / 256), unsigned(tiles)), dim3(256), 0, st,
+                       a, int32_t(a.stride / a.sweep));
+    return hipGetLastError();
+}
+
 hipError_t launch_scale_tick(const ScaleTickArgs &a, bool slice, int merge, hipStream_t st) {
     if (a.stride % kChunk || a.fanout < 1 || a.fanout > 16) return hipErrorInvalidValue;
+    if (slice && merge == 1 && a.sweep) return launch_scale_sweep(a, st);
     const size_t lds = scale_lds_bytes(a.stride, slice, a.ev.buf != nullptr) + size_t(a.lds_pad);
     const int policy = (a.nt_own ? 1 : 0) | (a.nt_src ? 2 : 0);
     if (slice) {

@@ -25,6 +25,9 @@ constexpr int kEntriesPerLane = 8;        // 16 B per lane per row chunk
 constexpr int kChunk = kScaleBlock * kEntriesPerLane;   // 2048 columns per block iteration
 constexpr int kEvStage = 512;             // event stream: LDS-staged records per wave (one chunk's worst case)
 constexpr int kMaxSegment = 1024;         // receiver segments sorted in LDS; longer ones are sorted in HBM
+constexpr int kSweepWidth = 512;          // sub-slab sweep: columns per sub-slab (one wave at 16 B per lane)
+constexpr int kSweepBatch = 64;           // sub-slab sweep: rows per workgroup (16 per wave)
+constexpr int kSweepMaxSeg = 64;          // ... and the messages a wave orders in registers (one per lane)
 constexpr int kDigSlots = 64;             // atomic sharding of the per-tick digest
 enum : int { kDigRounds = 0, kDigMerges, kDigSent, kDigDropped, kDigDelivered, kDigJoins,
              kDigRemoves, kDigHash, kDigFields };
@@ -83,6 +86,12 @@ struct ScaleTickArgs {
                                  // segment is longer than kMaxSegment (deferred to
                                  // scale_long_kernel); null: the tile appends nothing (the other
                                  // tiles of a shared CSR)
+    // sub-slab sweep (scale_sweep_kernel)
+    int32_t sweep;               // 0: one workgroup per row; else the sub-slab width W (512, 1024, 2048)
+    int32_t sweep_seg;           // the sweep defers rows with more messages (kSweepMaxSeg; tests: less)
+    int32_t *cnt_sub;            // [stride / W][n] member counts per sub-slab (sweep_count_kernel
+                                 // sums them into cnt_cur)
+    int32_t *mid_list;           // as long_list, for the rows with sweep_seg < k <= kMaxSegment
 };
 
 __host__ __device__ inline unsigned long long event_record(uint32_t kind, uint32_t t, uint32_t r,
@@ -118,7 +127,11 @@ __device__ inline void wave_append_events(unsigned long long *buf, unsigned long
 
 // merge: 0 = per-entry scalar form, 1 = packed 16-bit form (v_pk_* / v_bfi_b32)
 hipError_t launch_scale_init(const ScaleTickArgs &a, bool slice, hipStream_t st);
+// a.sweep != 0 (slice form, packed merge, plain protocol): the sub-slab sweep
 hipError_t launch_scale_tick(const ScaleTickArgs &a, bool slice, int merge, hipStream_t st);
+// after a sweep launch: cnt_cur of `tiles` tiles (a = the first one's args; their cnt_sub and
+// cnt_cur lie one after the other) from the per-sub-slab counts
+hipError_t launch_sweep_counts(const ScaleTickArgs &a, int32_t tiles, hipStream_t st);
 // the rows every tick-kernel launch of this tick deferred (k > kMaxSegment): tpl[2 * g + parity]
 // = local tile g's args at tick parity (dig at tick 0); a = tile 0's args of this tick
 hipError_t launch_scale_long(const ScaleTickArgs &a, const ScaleTickArgs *tpl, int32_t ntiles, bool slice,

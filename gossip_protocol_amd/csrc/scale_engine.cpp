@@ -101,6 +101,10 @@ struct gsp_scale {
     std::vector<hipEvent_t> free_events;
     gsp_scale_perf perf{};
 
+    void recycle(const Timed &t) {     // a tick's three events back to the pool
+        for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
+    }
+
     hipEvent_t event() {
         if (!free_events.empty()) {
             hipEvent_t e = free_events.back();
@@ -142,42 +146,43 @@ struct gsp_scale {
         // row layout's shard 0 broadcast
         a.intro = (rowmode && sh.row0 != 0) ? sh.intro_buf.p : sh.table[(t + 1) & 1].p;
         a.intro_list = p.policy.intro_list;
-        const Shard &s0 = local[0];
+        const Shard &o = owner(sh);    // shared: shard 0 (its CSR, counts, picks and bitmaps)
         // shared: cnt_all[tick parity][G][n], so this tick's slice counts never overwrite the
         // tick-(t - 1) counts another shard's JOINREP still reads
         const size_t gn = size_t(shards) * size_t(p.n);
-        a.intro_cnt = sliced ? (shared ? s0.cnt_all.p + size_t((t + 1) & 1) * gn : sh.cnt_all.p) : nullptr;
+        a.intro_cnt = sliced ? o.cnt_all.p + (shared ? size_t((t + 1) & 1) * gn : 0) : nullptr;
         a.shards = shards;
         a.shard = sh.g;
         a.own_hb = sh.own_hb.p;
-        a.cnt_prev = (shared ? s0 : sh).cnt_total[(t + 1) & 1].p;
-        a.cnt_cur = shared ? s0.cnt_all.p + size_t(t & 1) * gn + size_t(sh.g) * size_t(p.n)
+        a.cnt_prev = o.cnt_total[(t + 1) & 1].p;
+        a.cnt_cur = shared ? o.cnt_all.p + size_t(t & 1) * gn + size_t(sh.g) * size_t(p.n)
                   : sliced ? sh.cnt_slice.p : sh.cnt_total[t & 1].p;
-        a.off = (shared ? s0 : sh).off.p;
-        a.csr_src = (shared ? s0 : sh).csr_src.p;
+        a.off = o.off.p;
+        a.csr_src = o.csr_src.p;
         a.csr_slot = rowmode ? sh.x.csr_slot.p : nullptr;
         a.out_dst = sh.out_dst.p;
         a.deg = sh.deg.p;
-        a.ping = (shared ? s0 : sh).ping.p;
-        a.bitmap = shared ? s0.bitmap.p + size_t(sh.g - rank) * size_t(p.n) * size_t(stride / 8) : sh.bitmap.p;
+        a.ping = o.ping.p;
+        a.bitmap = o.bitmap.p + (shared ? size_t(sh.g - rank) * size_t(p.n) * size_t(stride / 8) : 0);
         a.dig = sh.dig.p + size_t(t) * gsp::kDigSlots * gsp::kDigFields;
         a.err = local[0].err.p;        // one flag for every shard held here
         a.max_segment = max_segment;
         a.ev = sh.ev.args();
         // the rows this tile's CSR defers (k > kMaxSegment): appended by the CSR's owner only
-        a.long_list = &sh == &owner(sh) ? long_list(sh, t) : nullptr;
+        a.long_list = owns_csr(sh) ? long_list(sh, t) : nullptr;
         if (sweep && merge == 1) {
             a.sweep = sweep;
             a.sweep_seg = sweep_seg;
             const size_t per = size_t(stride / sweep) * size_t(p.n);
-            a.cnt_sub = shared ? s0.cnt_sub.p + size_t(sh.g - rank) * per : sh.cnt_sub.p;
-            a.mid_list = &sh == &owner(sh) ? mid_list(sh, t) : nullptr;
+            a.cnt_sub = o.cnt_sub.p + (shared ? size_t(sh.g - rank) * per : 0);
+            a.mid_list = owns_csr(sh) ? mid_list(sh, t) : nullptr;
         }
         return a;
     }
 
     // the shard whose receiver CSR a shard reads (shared column tiles: shard 0's)
     const Shard &owner(const Shard &sh) const { return shared ? local[0] : sh; }
+    bool owns_csr(const Shard &sh) const { return &sh == &owner(sh); }
     int32_t *long_list(const Shard &sh, int32_t t) const {
         const Shard &o = owner(sh);
         return o.long_list.p + size_t(t & 1) * size_t(1 + o.rows);
@@ -277,7 +282,7 @@ int shard_alloc(gsp_scale *s, Shard &sh) {
     GSP_HIP(sh.csr_src.alloc(size_t(n) * s->p.fanout));
     GSP_HIP(sh.err.alloc(1));
     GSP_HIP(sh.tile_sum.alloc(size_t(n) / 4096 + 1));
-    if (!s->shared || &sh == &s->local[0]) {
+    if (s->owns_csr(sh)) {
         GSP_HIP(sh.long_list.alloc(2 * (rows + 1)));
         GSP_HIP(hipMemsetAsync(sh.long_list.p, 0, 2 * (rows + 1) * 4, st));
         if (s->sweep) {
@@ -285,9 +290,9 @@ int shard_alloc(gsp_scale *s, Shard &sh) {
             GSP_HIP(hipMemsetAsync(sh.mid_list.p, 0, 2 * (rows + 1) * 4, st));
         }
     }
-    if (s->sweep && (!s->shared || &sh == &s->local[0]))
+    if (s->sweep && s->owns_csr(sh))
         GSP_HIP(sh.cnt_sub.alloc(size_t(s->stride / s->sweep) * size_t(n) * (s->shared ? s->local.size() : 1)));
-    if (s->sliced && (!s->shared || &sh == &s->local[0])) {
+    if (s->sliced && s->owns_csr(sh)) {
         GSP_HIP(sh.cnt_slice.alloc(size_t(n)));
         GSP_HIP(sh.cnt_all.alloc(size_t(n) * s->shards * (s->shared ? 2 : 1)));
         // + 1: the capacity flag rides the all-reduce MAX of the picks (exchange_picks)
@@ -475,7 +480,7 @@ int join_sends(gsp_scale *s, int32_t t) {
     const int64_t cnt = s->plan.count(t + 1);
     if (!s->joins || cnt == 0) return GSP_OK;
     for (Shard &sh : s->local) {
-        if (s->shared && &sh != &s->local[0]) continue;   // one CSR (shard 0's deg)
+        if (!s->owns_csr(sh)) continue;   // one CSR (shard 0's deg)
         gsp::JoinSendArgs j{};
         j.joiners = sh.joiners.p + s->plan.first(t + 1);
         j.count = int32_t(cnt);
@@ -517,7 +522,7 @@ int join_scatter(gsp_scale *s, int32_t t) {
     const int64_t cnt = s->plan.count(t);
     if (!s->joins || cnt == 0) return GSP_OK;
     for (Shard &sh : s->local) {
-        if (s->shared && &sh != &s->local[0]) continue;
+        if (!s->owns_csr(sh)) continue;
         GSP_HIP(gsp::launch_join_scatter(sh.joiners.p + s->plan.first(t), sh.join_ok.p + s->plan.first(t),
                                          int32_t(cnt), s->rowmode ? sh.row0 : 0,
                                          s->rowmode ? sh.rows : s->p.n, sh.off.p, sh.fill.p, sh.csr_src.p,
@@ -535,9 +540,7 @@ int collect_timing(gsp_scale *s) {
         s->perf.csr_ms += a;
         s->perf.merge_ms += b;
         s->perf.merge_launches++;
-        s->free_events.push_back(t.a);
-        s->free_events.push_back(t.b);
-        s->free_events.push_back(t.c);
+        s->recycle(t);
     }
     s->pending.clear();
     if (s->rowmode)
@@ -734,11 +737,7 @@ int gsp_scale_destroy(gsp_scale *s) {
     if (!s) return GSP_OK;
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
-    for (auto &t : s->pending) {
-        s->free_events.push_back(t.a);
-        s->free_events.push_back(t.b);
-        s->free_events.push_back(t.c);
-    }
+    for (auto &t : s->pending) s->recycle(t);
     for (hipEvent_t e : s->free_events) (void)hipEventDestroy(e);
     for (Shard &sh : s->local) sh.release();
     s->long_tpl.release();
@@ -783,7 +782,7 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
             }
         } else {
             for (Shard &sh : s->local) {
-                if (s->shared && &sh != &s->local[0]) continue;   // one CSR for every shard
+                if (!s->owns_csr(sh)) continue;   // one CSR for every shard
                 GSP_HIP(gsp::launch_exclusive_scan(sh.deg.p, sh.off.p, n, sh.tile_sum.p, s->st));
                 GSP_HIP(hipMemsetAsync(sh.fill.p, 0, size_t(n) * 4, s->st));
                 GSP_HIP(gsp::launch_scatter(sh.out_dst.p, slots, s->p.fanout, 0, sh.off.p, sh.fill.p,

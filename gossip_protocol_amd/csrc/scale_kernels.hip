@@ -15,133 +15,16 @@
 // scale_sweep_kernel runs the same tick of a column tile of the plain protocol one wave per
 // (row, 512-column sub-slab), sub-slab by sub-slab, so that the sender re-reads of the previous
 // table are served by the Infinity Cache.
+// The steps of one lane vector (merge, sender bump, JOINREP, own column, TREMOVE scan, event
+// staging and flush, row deferral) are the functions of scale_row.hpp: the row forms here call
+// them in tick order and hold no copy of a protocol rule (DESIGN.md "One step, one function").
 #include "join_kernels.hpp"
 #include "philox.hpp"
-#include "scale_kernels.hpp"
-#include "wave_ops.hpp"
+#include "scale_row.hpp"
 
 namespace gsp {
 
 namespace {
-
-__device__ inline uint64_t event_mix(uint32_t kind, uint32_t t, uint32_t r, uint32_t x) {
-    uint64_t z = (uint64_t(kind) << 62) | (uint64_t(t & 0xFFFFF) << 42) |
-                 (uint64_t(r & 0x1FFFFF) << 21) | uint64_t(x & 0x1FFFFF);
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// ---- scalar form: one entry at a time ---------------------------------------------------
-// Merge one payload entry v (the sender's) into the receiver's entry e (both packed
-// hb << 5 | ts5, 0 = absent):
-//   present: max-merge, ts = now only on a strict heartbeat increase (MP1Node.cpp:247-251)
-//   absent:  copy v when v is present and fresh, t - ts_v < TREMOVE (MP1Node.cpp:294)
-__device__ inline uint32_t merge_entry(uint32_t e, uint32_t v, uint32_t t5, uint32_t tr) {
-    const uint32_t he = e >> 5, hv = v >> 5;
-    const uint32_t upd = (hv > he) ? ((v & 0xFFE0u) | t5) : e;
-    const uint32_t fresh = ((t5 - v) & 31u) < tr;
-    const uint32_t add = (v != 0u && fresh) ? v : 0u;
-    return e ? upd : add;
-}
-
-__device__ inline uint32_t merge_word_scalar(uint32_t e, uint32_t v, uint32_t t5, uint32_t tr) {
-    const uint32_t lo = merge_entry(e & 0xFFFFu, v & 0xFFFFu, t5, tr);
-    const uint32_t hi = merge_entry(e >> 16, v >> 16, t5, tr);
-    return lo | (hi << 16);
-}
-
-// ---- packed form: two entries per 32-bit word on the v_pk_*_u16 ALUs --------------------
-// hipcc folds min(sub_sat(a, b), 1) back into compares + selects, so the packed ops are
-// spelled out; every operand is a VGPR and nothing reads EXEC or the memory counters.
-__device__ inline uint32_t pk_max(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ inline uint32_t pk_min(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ inline uint32_t pk_sub(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ inline uint32_t pk_subc(uint32_t a, uint32_t b) {   // saturating at 0
-    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ inline uint32_t pk_mad(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r; asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
-}
-__device__ inline uint32_t bfi(uint32_t m, uint32_t a, uint32_t b) {   // (m & a) | (~m & b)
-    uint32_t r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b)); return r;
-}
-
-struct PackedConsts {
-    uint32_t one, t5x2, t32, tr, trm1, low5, hbmask, zero;
-};
-
-__device__ inline PackedConsts packed_consts(uint32_t t5, uint32_t tr) {
-    PackedConsts c;
-    c.one = 0x00010001u;
-    c.t5x2 = t5 | (t5 << 16);
-    c.t32 = c.t5x2 + 0x00200020u;
-    c.tr = tr | (tr << 16);
-    c.trm1 = (tr - 1) | ((tr - 1) << 16);
-    c.low5 = 0x001F001Fu;
-    c.hbmask = 0xFFE0FFE0u;
-    c.zero = 0u;
-    return c;
-}
-
-// Same function as merge_word_scalar (checked exhaustively over hb in {0..3, 31, 100, 1000,
-// 2046, 2047} x every ts5 x every t5 x tr in {1, 5, 20, 31}):
-//   present e:  m = max(v & hbmask, e); e' = m + (m != e) * t5
-//   absent e:   e' = v if v present and (t5 + 32 - ts5(v)) mod 32 < tr, else 0
-__device__ inline uint32_t merge_word_packed(uint32_t e, uint32_t v, const PackedConsts &c) {
-    const uint32_t m = pk_max(v & c.hbmask, e);
-    const uint32_t rp = pk_mad(pk_min(pk_sub(m, e), c.one), c.t5x2, m);
-    const uint32_t age = (c.t32 - (v & c.low5)) & c.low5;
-    const uint32_t ok = pk_min(pk_subc(c.tr, age), pk_min(v, c.one));
-    const uint32_t ra = v & pk_sub(c.zero, ok);
-    return bfi(pk_sub(c.zero, pk_min(e, c.one)), rp, ra);
-}
-
-// Replace entry i (runtime, 0..7) of a 16-B lane vector.  Only ever reached on the one
-// lane whose chunk holds the sender's or the receiver's own column, so the compare-select
-// chain (which keeps every index compile-time: no scratch) costs nothing in the stream.
-template <typename F>
-__device__ inline void patch16(uint4 &w, int i, F f) {
-    uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int q = 0; q < kEntriesPerLane; ++q) {
-        const int sh = (q & 1) * 16;
-        const uint32_t old = (ws[q >> 1] >> sh) & 0xFFFFu;
-        const uint32_t nv = f(old) & 0xFFFFu;
-        if (q == i) ws[q >> 1] = (ws[q >> 1] & ~(0xFFFFu << sh)) | (nv << sh);
-    }
-    w = make_uint4(ws[0], ws[1], ws[2], ws[3]);
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// 16-byte row accesses; kNT selects the non-temporal (streaming) cache policy.  It must be
-// a compile-time choice: a runtime select between the two forms is CSE'd into one plain load.
-template <bool kNT>
-__device__ inline uint4 ld16(const uint16_t *p) {
-    const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
-    u32x4 v;
-    if constexpr (kNT) v = __builtin_nontemporal_load(q);
-    else v = *q;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-template <bool kNT>
-__device__ inline void st16(uint16_t *p, const uint32_t (&w)[4]) {
-    u32x4 v;
-    v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-    u32x4 *q = reinterpret_cast<u32x4 *>(p);
-    if constexpr (kNT) __builtin_nontemporal_store(v, q);
-    else *q = v;
-}
-
-__device__ inline uint64_t wave_sum_u64(uint64_t v) { return wave_sum64(v); }
 
 // rank-th set bit (0-based) of a bitmap of `words` 32-bit words, by one wave; -1 if none.
 // lane_cnt / pre: this lane's popcount over its words and the exclusive prefix.
@@ -168,7 +51,7 @@ __device__ inline int32_t wave_select(W word, int32_t per, uint32_t lane_cnt, ui
     return int32_t(lane_of(uint32_t(col), __builtin_ffsll(owner) - 1));
 }
 
-__device__ inline uint32_t wave_excl_prefix(uint32_t v, int32_t, uint32_t *total) {
+__device__ inline uint32_t wave_excl_prefix(uint32_t v, uint32_t *total) {
     const uint32_t incl = wave_incl_scan(v);
     *total = lane_of(incl, 63);
     return incl - v;
@@ -324,7 +207,6 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
     int32_t k = 0;
     // a long segment (k > kMaxSegment): sorted in HBM, its first k - kMaxSegment messages are
     // merged by the premerge below and the chunk loop merges the rest from LDS
-    constexpr bool lng = kLong;
     if (!kInit) {
         const int32_t o0 = a.off[lr];
         k = a.off[lr + 1] - o0;
@@ -333,13 +215,12 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
             if (!kSlice && tid < F) a.out_dst[int64_t(lr) * F + tid] = -1;
             return;
         }
-        if (!lng && k > kMaxSegment) {   // deferred to scale_long_kernel (one list per CSR)
-            if (tid == 0 && a.long_list)
-                a.long_list[1 + atomicAdd(&a.long_list[0], 1)] = lr;
+        if (!kLong && k > kMaxSegment) {   // deferred to scale_long_kernel (one list per CSR)
+            if (tid == 0) defer_row(a.long_list, lr);
             return;
         }
     }
-    if constexpr (lng) {
+    if constexpr (kLong) {
         const int32_t o0 = a.off[lr];
         sort_long_segment(a.csr_src + o0, a.csr_slot ? a.csr_slot + o0 : nullptr, k);
         if (tid == 0) s_src[0] = a.csr_src[o0];           // the JOINREP test below
@@ -357,7 +238,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
             rank[q] = -1;
             if (i < k) {
                 val[q] = s_src[i];
-                slot[q] = a.csr_slot ? a.csr_slot[o0 + i] : val[q] - a.row0;
+                slot[q] = sender_slot(a, o0 + i, val[q]);
                 int32_t rk = 0;
                 for (int32_t j = 0; j < k; ++j) rk += s_src[j] < val[q];
                 rank[q] = rk;
@@ -388,11 +269,6 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
     const uint32_t tfx2 = tf | (tf << 16);
     const uint32_t t5m1 = uint32_t(t - 1) & 31u;                  // the senders' tick, mod 32
     const uint32_t t32m1 = (t5m1 | (t5m1 << 16)) + 0x00200020u;
-    // kTfail: drop the payload entries the sender had suspected when it sent (packed pair)
-    auto gossiped = [&](uint32_t w) -> uint32_t {
-        const uint32_t age = (t32m1 - (w & pc.low5)) & pc.low5;
-        return w & pk_sub(pc.zero, pk_min(pk_subc(tfx2, age), pc.one));
-    };
     // kSwim: the probe of t - 1 (target pcol, read before wave 0 rewrites a.ping[lr] below the
     // block reduction's barrier); one direct + a.swim - 1 indirect paths, each with a drop draw
     int32_t pcol = -1;
@@ -415,7 +291,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
     uint16_t *own_cur = a.cur + int64_t(lr) * stride;
     uint32_t live = 0, joins = 0, removes = 0;
     uint64_t hsum = 0;
-    if constexpr (lng) {
+    if constexpr (kLong) {
         // Premerge of a long segment: the JOINREP and the GOSSIPs at sorted positions [jr, pend)
         // merged in order into the own row, written to this tick's row (read back by the chunk
         // loop as its own row, so the chunk loop merges senders [pend, k) after them: the same
@@ -429,37 +305,16 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
             const int64_t lc0 = c0 + int64_t(tid) * kEntriesPerLane, gc0 = a.col0 + lc0;
             uint4 e = ld16<false>(own_prev + lc0);
             const uint4 b = e;
-            if (jr) {
-                const int64_t d0 = -gc0;
-                if (d0 >= 0 && d0 < kEntriesPerLane)
-                    patch16(e, int(d0), [t5](uint32_t old) { return old ? ((((old >> 5) + 1u) << 5) | t5)
-                                                                        : ((1u << 5) | t5); });
-                for (int32_t q = 0; q < njc; ++q) {
-                    const int64_t dq = int64_t(s_jc[q]) - gc0;
-                    const uint32_t v = s_jv[q];
-                    if (dq >= 0 && dq < kEntriesPerLane)
-                        patch16(e, int(dq), [v, t5, tr](uint32_t old) { return merge_entry(old, v, t5, tr); });
-                }
-            }
+            if (jr) merge_joinrep(e, gc0, njc, s_jc, s_jv, t5, tr);
             for (int32_t j = jr; j < pend; ++j) {
                 const int32_t sj = a.csr_src[o0 + j];
-                const int32_t sl = a.csr_slot ? a.csr_slot[o0 + j] : sj - a.row0;
-                const uint16_t *row = sl >= 0 ? a.prev + int64_t(sl) * stride : a.remote + int64_t(-sl - 1) * stride;
-                uint4 v = ld16<false>(row + lc0);
-                if (kTfail) {
-                    v.x = gossiped(v.x);
-                    v.y = gossiped(v.y);
-                    v.z = gossiped(v.z);
-                    v.w = gossiped(v.w);
-                }
-                e.x = merge_word_scalar(e.x, v.x, t5, tr);
-                e.y = merge_word_scalar(e.y, v.y, t5, tr);
-                e.z = merge_word_scalar(e.z, v.z, t5, tr);
-                e.w = merge_word_scalar(e.w, v.w, t5, tr);
-                const int64_t ds = int64_t(sj) - gc0;
-                if (ds >= 0 && ds < kEntriesPerLane)
-                    patch16(e, int(ds), [t5](uint32_t old) { return (((old >> 5) + 1u) << 5) | t5; });
+                uint4 v = ld16<false>(sender_row(a, sender_slot(a, o0 + j, sj)) + lc0);
+                if (kTfail) gossiped_vec(v, pc, tfx2, t32m1);
+                merge_vec<0>(e, v, pc, t5, tr);
+                bump_sender(e, sj, gc0, t5);
             }
+            // The join count is spelled out here, not scan_entries: no TREMOVE scan runs yet (the
+            // chunk loop's does), and the two exclusions above are this premerge's alone.
             const uint32_t bw[4] = {b.x, b.y, b.z, b.w};
             const uint32_t ew[4] = {e.x, e.y, e.z, e.w};
 #pragma unroll
@@ -482,7 +337,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
         for (int32_t i = tid; i < kMaxSegment; i += kScaleBlock) {
             const int32_t sj = a.csr_src[o0 + pend + i];
             s_src[i] = sj;
-            s_slot[i] = a.csr_slot ? a.csr_slot[o0 + pend + i] : sj - a.row0;
+            s_slot[i] = sender_slot(a, o0 + pend + i, sj);
         }
         __syncthreads();
         own_prev = own_cur;
@@ -496,17 +351,6 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
     uint32_t ev_fill = 0;                                           // wave-uniform
     unsigned long long *const ev_buf = a.ev.buf ? ev_stripe_buf(a.ev) : nullptr;
     unsigned long long *const ev_count = ev_stripe_count(a.ev);
-    auto ev_flush = [&](uint32_t fill, unsigned long long base) {   // fill records -> ring
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t i = uint32_t(lane); i < fill; i += 64) {
-            const uint32_t s = s_ev[i];
-            if (int64_t(base + i) < a.ev.cap)
-                ev_buf[base + i] = event_record(s >> 30, uint32_t(t), uint32_t(r), s & 0x3FFFFFFFu);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
 
     // kPipe: the first 4 sender rows as wave-uniform (scalar) pointers, and the request of one
     // chunk's own + sender vectors (16 B per lane each) issued one chunk ahead
@@ -522,8 +366,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             pv[u] = make_uint4(0u, 0u, 0u, 0u);
-            const int32_t sl = __builtin_amdgcn_readfirstlane(jr + u < k ? s_slot[jr + u] : 0);
-            srow[u] = sl >= 0 ? a.prev + int64_t(sl) * stride : a.remote + int64_t(-sl - 1) * stride;
+            srow[u] = sender_row(a, __builtin_amdgcn_readfirstlane(jr + u < k ? s_slot[jr + u] : 0));
         }
         issue(int64_t(tid) * kEntriesPerLane);
     }
@@ -561,18 +404,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
                 e = ld16<kNtOwn>(own_prev + lc0);
             }
             w0[0] = e.x; w0[1] = e.y; w0[2] = e.z; w0[3] = e.w;
-            if (jr) {                         // the JOINREP: the introducer's sender entry
-                const int64_t d0 = -gc0;      // (MP1Node.cpp:237-243), then its chosen members
-                if (d0 >= 0 && d0 < kEntriesPerLane)
-                    patch16(e, int(d0), [t5](uint32_t old) { return old ? ((((old >> 5) + 1u) << 5) | t5)
-                                                                        : ((1u << 5) | t5); });
-                for (int32_t q = 0; q < njc; ++q) {
-                    const int64_t dq = int64_t(s_jc[q]) - gc0;
-                    const uint32_t v = s_jv[q];
-                    if (dq >= 0 && dq < kEntriesPerLane)
-                        patch16(e, int(dq), [v, t5, tr](uint32_t old) { return merge_entry(old, v, t5, tr); });
-                }
-            }
+            if (jr) merge_joinrep(e, gc0, njc, s_jc, s_jv, t5, tr);
             for (int32_t j0 = jr; j0 < k; j0 += 4) {
                 uint4 v[4];
                 if (kPipe && j0 == jr) {
@@ -581,43 +413,18 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
                 } else {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        if (j0 + u < k) {
-                            const int32_t sl = s_slot[j0 + u];
-                            const uint16_t *row = sl >= 0 ? a.prev + int64_t(sl) * stride
-                                                          : a.remote + int64_t(-sl - 1) * stride;
-                            v[u] = ld16<kNtSrc>(row + lc0);
-                        }
+                        if (j0 + u < k) v[u] = ld16<kNtSrc>(sender_row(a, s_slot[j0 + u]) + lc0);
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (j0 + u >= k) break;
-                    if (kTfail) {
-                        v[u].x = gossiped(v[u].x);
-                        v[u].y = gossiped(v[u].y);
-                        v[u].z = gossiped(v[u].z);
-                        v[u].w = gossiped(v[u].w);
-                    }
-                    if (kMerge == 1) {
-                        e.x = merge_word_packed(e.x, v[u].x, pc);
-                        e.y = merge_word_packed(e.y, v[u].y, pc);
-                        e.z = merge_word_packed(e.z, v[u].z, pc);
-                        e.w = merge_word_packed(e.w, v[u].w, pc);
-                    } else {
-                        e.x = merge_word_scalar(e.x, v[u].x, t5, tr);
-                        e.y = merge_word_scalar(e.y, v[u].y, t5, tr);
-                        e.z = merge_word_scalar(e.z, v[u].z, t5, tr);
-                        e.w = merge_word_scalar(e.w, v[u].w, t5, tr);
-                    }
-                    // the sender's own entry: hb + 1 and ts = now, or add (1, now)
-                    // (MP1Node.cpp:237-243); the sender's row never holds itself
-                    const int64_t ds = int64_t(s_src[j0 + u]) - gc0;
-                    if (ds >= 0 && ds < kEntriesPerLane)
-                        patch16(e, int(ds), [t5](uint32_t old) { return (((old >> 5) + 1u) << 5) | t5; });
+                    if (kTfail) gossiped_vec(v[u], pc, tfx2, t32m1);
+                    merge_vec<kMerge>(e, v[u], pc, t5, tr);
+                    bump_sender(e, s_src[j0 + u], gc0, t5);
                 }
             }
-            const int64_t dr = int64_t(r) - gc0;      // never list yourself (MP1Node.cpp:290)
-            if (dr >= 0 && dr < kEntriesPerLane) patch16(e, int(dr), [](uint32_t) { return 0u; });
+            clear_own(e, r, gc0);
             if (kSwim && pcol >= 0) {                 // the probe's answer (or its absence)
                 const int64_t dp = int64_t(pcol) - gc0;
                 if (dp >= 0 && dp < kEntriesPerLane)
@@ -627,70 +434,16 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
         }
 
         // TREMOVE scan, events and presence bits of the 8 entries
-        bool slow = !kInit;
-        uint32_t bits = 0;
-        if (kMerge == 1 && !kInit) {
-            uint32_t ev = 0, q = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t pe = pk_min(ws[i], pc.one);
-                const uint32_t age = (pc.t32 - (ws[i] & pc.low5)) & pc.low5;
-                ev |= pk_min(pk_subc(age, pc.trm1), pe);          // present and stale
-                ev |= pk_subc(pe, pk_min(w0[i], pc.one));          // absent before, present now
-                const uint32_t pg = kTfail ? pk_min(pe, pk_min(pk_subc(tfx2, age), pc.one)) : pe;
-                q |= ((pg | (pg >> 15)) & 3u) << (2 * i);
-            }
-            slow = ev != 0;
-            bits = q;
-        }
-        uint32_t evj = 0, evr = 0;            // this chunk's join / remove entries (event stream)
-        if (kInit || slow) {
-            bits = 0;
-#pragma unroll
-            for (int i = 0; i < kEntriesPerLane; ++i) {
-                const int sh = (i & 1) * 16;
-                uint32_t ent = (ws[i >> 1] >> sh) & 0xFFFFu;
-                if (!kInit && ent) {
-                    const uint32_t before = (w0[i >> 1] >> sh) & 0xFFFFu;
-                    if (((t5 - ent) & 31u) >= tr) {     // TREMOVE scan (MP1Node.cpp:340)
-                        removes++;
-                        hsum += event_mix(2, uint32_t(t), uint32_t(r), uint32_t(gc0 + i));
-                        ws[i >> 1] &= ~(0xFFFFu << sh);
-                        ent = 0;
-                        evr |= 1u << i;
-                    } else if (!before) {
-                        joins++;
-                        hsum += event_mix(1, uint32_t(t), uint32_t(r), uint32_t(gc0 + i));
-                        evj |= 1u << i;
-                    }
-                }
-                const bool counted = ent && (!kTfail || ((t5 - ent) & 31u) < tf);
-                bits |= (counted ? 1u : 0u) << i;
-            }
-        }
-        if (!kInit && ev_buf) {               // the event stream: stage this chunk's records
-            uint32_t both = ((a.ev.kinds & GSP_EVENTS_JOIN) ? evj : 0u) |
-                            ((a.ev.kinds & GSP_EVENTS_REMOVE) ? (evr << 8) : 0u);
-            const uint32_t cnt = uint32_t(__builtin_popcount(both));
-            if (__ballot(cnt > 0)) {          // wave-uniform
-                const uint32_t incl = wave_incl_scan(cnt);
-                const uint32_t total = lane_of(incl, 63);
-                if (ev_fill + total > uint32_t(kEvStage)) {
-                    unsigned long long base = 0;
-                    if (lane == 0) base = atomicAdd(ev_count, (unsigned long long)ev_fill);
-                    base = (uint64_t(lane_of(uint32_t(base >> 32), 0)) << 32) | lane_of(uint32_t(base), 0);
-                    ev_flush(ev_fill, base);
-                    ev_fill = 0;
-                }
-                uint32_t p = ev_fill + incl - cnt;
-                while (both) {
-                    const uint32_t b = uint32_t(__builtin_ffs(both) - 1);
-                    both &= both - 1;
-                    s_ev[p++] = ((b < 8 ? 1u : 2u) << 30) | uint32_t(gc0 + (b & 7u));
-                }
-                ev_fill += total;
-            }
-        }
+        uint32_t bits = 0, evj = 0, evr = 0;  // evj / evr: this chunk's join / remove entries
+        bool slow = true;
+        if constexpr (kMerge == 1 && !kInit) slow = screen_vec<kTfail>(ws, w0, pc, tfx2, bits);
+        if (slow) bits = scan_entries<kInit, kTfail>(ws, w0, t, r, gc0, tr, tf, joins, removes, hsum, evj, evr);
+        if (!kInit && ev_buf)                 // the event stream: stage this chunk's records
+            ev_fill = ev_stage(s_ev, ev_fill, evj, evr, a.ev.kinds, gc0, [&](uint32_t fill, uint32_t total) {
+                if (fill + total <= uint32_t(kEvStage)) return fill;
+                ev_flush(ev_buf, s_ev, fill, ev_reserve(ev_count, fill, lane), a.ev.cap, t, r, lane);
+                return 0u;
+            });
         live += __builtin_popcount(bits);
         st16<kNtOwn>(own_cur + lc0, ws);
         // presence bitmap: 8 bits per lane -> byte (lc0 / 8)
@@ -701,8 +454,8 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
     }
 
     // block reduction: live, joins, removes, hash
-    const uint64_t v0 = wave_sum_u64(live), v1 = wave_sum_u64(joins), v2 = wave_sum_u64(removes);
-    const uint64_t v3 = wave_sum_u64(hsum);
+    const uint64_t v0 = wave_sum64(live), v1 = wave_sum64(joins), v2 = wave_sum64(removes);
+    const uint64_t v3 = wave_sum64(hsum);
     if (lane == 0) { s_red[wave][0] = v0; s_red[wave][1] = v1; s_red[wave][2] = v2; s_red[wave][3] = v3; }
     if (!kInit && ev_buf && lane == 0) s_evf[wave] = ev_fill;
     __syncthreads();
@@ -713,7 +466,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
         __syncthreads();
         if (f0 + f1 + f2 + f3) {
             const uint32_t before = (wave > 0 ? f0 : 0u) + (wave > 1 ? f1 : 0u) + (wave > 2 ? f2 : 0u);
-            ev_flush(ev_fill, s_evbase + before);
+            ev_flush(ev_buf, s_ev, ev_fill, s_evbase + before, a.ev.cap, t, r, lane);
         }
     }
 
@@ -724,19 +477,13 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
             a.own_hb[lr] += 1;
             if (a.count_rounds) {
                 unsigned long long merges = 0;
-                if (jr) {                     // a JOINREP carries min(B, cnt0) members
-                    const int32_t c0 = a.cnt_prev[0];
-                    merges += 1ull + uint64_t(a.intro_list < c0 ? a.intro_list : c0);
-                }
+                if (jr) merges += joinrep_merges(a);
                 // the whole segment (a long one's premerged part too, from the sorted CSR)
                 int32_t ka = k;
-                if constexpr (lng) {
+                if constexpr (kLong) {
                     const int32_t o0 = a.off[lr];
                     ka = a.off[lr + 1] - o0;
-                    if (a.csr_src[o0] == kJoinRepSrc) {   // the JOINREP went to the premerge
-                        const int32_t c0 = a.cnt_prev[0];
-                        merges += 1ull + uint64_t(a.intro_list < c0 ? a.intro_list : c0);
-                    }
+                    if (a.csr_src[o0] == kJoinRepSrc) merges += joinrep_merges(a);   // it went to the premerge
                     for (int32_t j = a.csr_src[o0] == kJoinRepSrc ? 1 : 0; j < ka; ++j)
                         merges += 1ull + uint64_t(a.cnt_prev[a.csr_src[o0 + j]]);
                 } else {
@@ -759,7 +506,7 @@ __device__ __forceinline__ void scale_tick_row(const ScaleTickArgs &a, const int
         uint32_t lane_cnt = 0;
         for (int32_t w = 0; w < per; ++w) lane_cnt += __builtin_popcount(s_bits[lane * per + w]);
         uint32_t total = 0;
-        const uint32_t pre = wave_excl_prefix(lane_cnt, lane, &total);
+        const uint32_t pre = wave_excl_prefix(lane_cnt, &total);
         const int32_t cnt = int32_t(tot_live);
         const int32_t keff = F < cnt ? F : cnt;
         int32_t chosen[16];
@@ -865,8 +612,7 @@ __global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_e
             const int32_t k = int32_t(lane_of(uint32_t(m_k), i));
             if (k < 0) continue;
             if (k <= a.sweep_seg) break;
-            int32_t *const list = k > kMaxSegment ? a.long_list : a.mid_list;
-            if (sub == 0 && lane == 0 && list) list[1 + atomicAdd(&list[0], 1)] = lr0 + i;
+            if (sub == 0 && lane == 0) defer_row(k > kMaxSegment ? a.long_list : a.mid_list, lr0 + i);
         }
         return i;
     };
@@ -886,11 +632,11 @@ __global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_e
             if (lane < k) merges += 1ull + uint64_t(a.cnt_prev[sid]);
             delivered += lane == 0 ? uint32_t(k) : 0u;
         }
-        e = ld16<false>(a.prev + int64_t(lr0 + i) * stride + lc0);
+        e = ld16<false>(local_row(a, lr0 + i) + lc0);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             if (u < k)
-                sv[u] = ld16<false>(a.prev + int64_t(int32_t(lane_of(uint32_t(sorted), u)) - a.row0) * stride + lc0);
+                sv[u] = ld16<false>(local_row(a, int32_t(lane_of(uint32_t(sorted), u)) - a.row0) + lc0);
     };
 
     // the rows are pipelined: row i + 1's vectors are requested before row i is merged
@@ -914,95 +660,32 @@ __global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_e
                 for (int u = 0; u < 4; ++u) {
                     if (j0 + u < k) {
                         ss[u] = int32_t(lane_of(uint32_t(sorted), j0 + u));
-                        if (j0) sv[u] = ld16<false>(a.prev + int64_t(ss[u] - a.row0) * stride + lc0);
+                        if (j0) sv[u] = ld16<false>(local_row(a, ss[u] - a.row0) + lc0);
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (j0 + u >= k) break;
-                    e.x = merge_word_packed(e.x, sv[u].x, pc);
-                    e.y = merge_word_packed(e.y, sv[u].y, pc);
-                    e.z = merge_word_packed(e.z, sv[u].z, pc);
-                    e.w = merge_word_packed(e.w, sv[u].w, pc);
-                    // the sender's own entry: hb + 1 and ts = now, or add (1, now)
-                    const int64_t ds = int64_t(ss[u]) - gc0;
-                    if (ds >= 0 && ds < kEntriesPerLane)
-                        patch16(e, int(ds), [t5](uint32_t old) { return (((old >> 5) + 1u) << 5) | t5; });
+                    merge_vec<1>(e, sv[u], pc, t5, tr);
+                    bump_sender(e, ss[u], gc0, t5);
                 }
             }
-            const int64_t dr = int64_t(r) - gc0;      // never list yourself
-            if (dr >= 0 && dr < kEntriesPerLane) patch16(e, int(dr), [](uint32_t) { return 0u; });
+            clear_own(e, r, gc0);
             uint32_t ws[4] = {e.x, e.y, e.z, e.w};
 
-            // TREMOVE scan, events and presence bits of the 8 entries (as the block form)
-            uint32_t ev = 0, bits = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t pe = pk_min(ws[q], pc.one);
-                const uint32_t age = (pc.t32 - (ws[q] & pc.low5)) & pc.low5;
-                ev |= pk_min(pk_subc(age, pc.trm1), pe);          // present and stale
-                ev |= pk_subc(pe, pk_min(w0[q], pc.one));          // absent before, present now
-                bits |= ((pe | (pe >> 15)) & 3u) << (2 * q);
-            }
-            uint32_t evj = 0, evr = 0;
-            if (ev != 0) {
-                bits = 0;
-#pragma unroll
-                for (int q = 0; q < kEntriesPerLane; ++q) {
-                    const int sh = (q & 1) * 16;
-                    uint32_t ent = (ws[q >> 1] >> sh) & 0xFFFFu;
-                    if (ent) {
-                        const uint32_t before = (w0[q >> 1] >> sh) & 0xFFFFu;
-                        if (((t5 - ent) & 31u) >= tr) {     // TREMOVE scan (MP1Node.cpp:340)
-                            removes++;
-                            hsum += event_mix(2, uint32_t(t), uint32_t(r), uint32_t(gc0 + q));
-                            ws[q >> 1] &= ~(0xFFFFu << sh);
-                            ent = 0;
-                            evr |= 1u << q;
-                        } else if (!before) {
-                            joins++;
-                            hsum += event_mix(1, uint32_t(t), uint32_t(r), uint32_t(gc0 + q));
-                            evj |= 1u << q;
-                        }
-                    }
-                    bits |= (ent ? 1u : 0u) << q;
-                }
-            }
-            if (ev_buf) {                         // the event stream: stage this vector's records
-                uint32_t both = ((a.ev.kinds & GSP_EVENTS_JOIN) ? evj : 0u) |
-                                ((a.ev.kinds & GSP_EVENTS_REMOVE) ? (evr << 8) : 0u);
-                const uint32_t cnt = uint32_t(__builtin_popcount(both));
-                if (__ballot(cnt > 0)) {          // wave-uniform
-                    const uint32_t incl = wave_incl_scan(cnt);
-                    uint32_t p = ev_fill + incl - cnt;
-                    while (both) {
-                        const uint32_t b = uint32_t(__builtin_ffs(both) - 1);
-                        both &= both - 1;
-                        s_ev[p++] = ((b < 8 ? 1u : 2u) << 30) | uint32_t(gc0 + (b & 7u));
-                    }
-                    ev_fill += lane_of(incl, 63);
-                }
-            }
+            uint32_t bits = 0, evj = 0, evr = 0;
+            if (screen_vec<false>(ws, w0, pc, 0u, bits))
+                bits = scan_entries<false, false>(ws, w0, t, r, gc0, tr, 0u, joins, removes, hsum, evj, evr);
+            if (ev_buf)                           // the event stream: a sub-slab's records always fit
+                ev_fill = ev_stage(s_ev, ev_fill, evj, evr, a.ev.kinds, gc0, [](uint32_t fill, uint32_t) { return fill; });
             live += __builtin_popcount(bits);
             st16<kNtCur>(own_cur + lc0, ws);
             a.bitmap[int64_t(lr) * (stride >> 3) + (lc0 >> 3)] = uint8_t(bits);
         }
         const uint32_t row_live = wave_sum32(live);
         if (lane == i) m_cnt = row_live;
-        if (ev_fill) {                            // the item's one ring reservation
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(ev_count, (unsigned long long)ev_fill);
-            base = (uint64_t(lane_of(uint32_t(base >> 32), 0)) << 32) | lane_of(uint32_t(base), 0);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (uint32_t q = uint32_t(lane); q < ev_fill; q += 64) {
-                const uint32_t s = s_ev[q];
-                if (int64_t(base + q) < a.ev.cap)
-                    ev_buf[base + q] = event_record(s >> 30, uint32_t(t), uint32_t(r), s & 0x3FFFFFFFu);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+        if (ev_fill)                              // the item's one ring reservation
+            ev_flush(ev_buf, s_ev, ev_fill, ev_reserve(ev_count, ev_fill, lane), a.ev.cap, t, r, lane);
         i = ni;
         k = nk;
         sorted = nsorted;
@@ -1105,7 +788,7 @@ __global__ void __launch_bounds__(256) scale_resolve_kernel(ScaleResolveArgs a) 
     }
     const uint32_t c = lane < a.shards ? uint32_t(a.cnt_all[int64_t(lane) * a.n + s]) : 0u;
     uint32_t total = 0;
-    const uint32_t cpre = wave_excl_prefix(c, lane, &total);
+    const uint32_t cpre = wave_excl_prefix(c, &total);
     if (lane == 0) a.cnt_total[s] = int32_t(total);
     const int32_t cnt = int32_t(total);
     const int32_t keff = F < cnt ? F : cnt;
@@ -1126,7 +809,7 @@ __global__ void __launch_bounds__(256) scale_resolve_kernel(ScaleResolveArgs a) 
             lane_cnt = 0;
             for (int32_t w = 0; w < per; ++w) lane_cnt += __builtin_popcount(bm[lane * per + w]);
             uint32_t tot = 0;
-            pre = wave_excl_prefix(lane_cnt, lane, &tot);
+            pre = wave_excl_prefix(lane_cnt, &tot);
             bm_g = g;
         }
         const uint32_t local = rk - __shfl(cpre, g, 64);
@@ -1173,7 +856,7 @@ __global__ void scale_finalize_kernel(ScaleResolveArgs a) {
         }
         a.out_dst[i] = d;
     }
-    dropped = wave_sum_u64(dropped);
+    dropped = wave_sum64(dropped);
     if ((threadIdx.x & 63) == 0 && dropped && a.count_rounds)
         atomicAdd(&a.dig[(blockIdx.x % kDigSlots) * kDigFields + kDigDropped], dropped);
 }

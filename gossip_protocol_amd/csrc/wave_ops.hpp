@@ -31,6 +31,10 @@ __device__ __forceinline__ uint32_t lane_of(uint32_t x, int32_t l) {
     return uint32_t(__builtin_amdgcn_readlane(int(x), l));
 }
 
+__device__ __forceinline__ uint64_t lane_of(uint64_t x, int32_t l) {      // two v_readlane
+    return (uint64_t(lane_of(uint32_t(x >> 32), l)) << 32) | lane_of(uint32_t(x), l);
+}
+
 __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) { return lane_of(wave_incl_scan(v), 63); }
 
 // 64-bit wave sum (mod 2^64) from three 32-bit scans: the low word in two 16-bit halves (each

@@ -11,6 +11,12 @@
 //   all-reduce MAX of the resolved peer choices                (n * fanout * 4 B)
 // over RCCL (one process per GPU) or, for a group of shards inside one process, device
 // copies on the group's stream (used to test the sharded path on one GPU).
+//
+// The skeleton shared with the partial-view engine is engine_host.hpp: stream, event pool and
+// timing, failure / join schedule, communicator, capacity flag, common shard buffers, the
+// single-shard CSR build, JOINREP sends, the call into the row exchange and the C-ABI bodies
+// that are the same code.  Here: the tables and column / slice state, the tick arguments, the
+// count / pick exchanges, the sweep and the long-row table.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -20,23 +26,15 @@
 #include <memory>
 #include <vector>
 
-#include "common.hpp"
-#include "join_kernels.hpp"
+#include "engine_host.hpp"
 #include "philox.hpp"
-#include "policy.hpp"
-#include "rowx_host.hpp"
-#include "scale_kernels.hpp"
 
 namespace {
 
-struct Shard {
-    int32_t g = 0;
+struct Shard : gsp::ShardCore {
     int32_t col0 = 0;
-    int32_t row0 = 0, rows = 0;    // row layout: rows [row0, row0 + rows); else all n rows
-    gsp::RowxBufs x;               // row layout exchange buffers
     gsp::DevBuf<uint16_t> table[2];
-    gsp::DevBuf<int32_t> own_hb, fail_tick, cnt_total[2], cnt_slice, cnt_all, out_dst, picks,
-        ping, deg, off, fill, csr_src, err, tile_sum, start_tick, joiners, join_ok,
+    gsp::DevBuf<int32_t> cnt_total[2], cnt_slice, cnt_all, picks,
         long_list,                 // [2][1 + rows] by tick parity: rows with k > kMaxSegment
                                    // (a CSR owner's: shard 0 of a shared group, else each)
         mid_list,                  // sub-slab sweep: the same for kSweepMaxSeg < k <= kMaxSegment
@@ -44,46 +42,28 @@ struct Shard {
                                    // shared group, else [stride / W][n] on each shard
     gsp::DevBuf<uint16_t> intro_buf;   // row layout, shards != 0: node 0's row of the last tick
     gsp::DevBuf<uint8_t> bitmap;
-    gsp::DevBuf<unsigned long long> dig;
-    gsp::EvRing ev;
 
     void release() {
         for (int b = 0; b < 2; ++b) { table[b].release(); cnt_total[b].release(); }
-        for (auto *x : {&own_hb, &fail_tick, &cnt_slice, &cnt_all, &out_dst, &picks, &ping, &deg, &off,
-                        &fill, &csr_src, &err, &tile_sum, &start_tick, &joiners, &join_ok, &long_list, &mid_list, &cnt_sub})
-            x->release();
+        for (auto *b : {&cnt_slice, &cnt_all, &picks, &long_list, &mid_list, &cnt_sub}) b->release();
         intro_buf.release();
         bitmap.release();
-        dig.release();
-        ev.release();
-        x.release();
+        ShardCore::release();
     }
 };
 
 }  // namespace
 
-struct gsp_scale {
+struct gsp_scale : gsp::EngineCore {
     gsp_scale_params p{};
-    int device = 0;
-    hipStream_t st = nullptr;
-    int32_t shards = 1;        // G: column shards in the whole job
-    int32_t rank = 0;          // first shard index held by this engine
     bool sliced = false;       // column layout (G > 1)
     bool shared = false;       // column layout, every shard in this process on one device (an
                                // in-process group): the shards share shard 0's CSR, counts,
                                // picks and sends, so the tick has no exchange at all -- G
                                // column tiles of one GPU's job (DESIGN.md "Column tiles")
-    bool rowmode = false;      // row layout (G > 1): sender rows move between shards
-    int64_t pair_cap = 0, msg_cap = 0;
-    gsp::RowxState rowx;       // row layout: the exchange's count ring and posted sizes
-    int32_t *h_err = nullptr;  // pinned mirror of the shards' capacity flags, refreshed by an
-                               // async copy at the end of every gsp_scale_step call
     int32_t max_segment = INT32_MAX;     // segments past kMaxSegment take the HBM sort
-    ncclComm_t comm = nullptr; // one shard per process when set
     int64_t width = 0;         // n rounded up to 2048 * G
     int64_t stride = 0;        // columns per shard
-    int32_t tick = 0;
-    bool timing = true;
     int policy = 5;            // bit 0 nt own row, bit 1 nt sender rows, bit 2 pipelined loads
     int merge = 1;             // 1 packed 16-bit merge, 0 per-entry form
     int32_t lds_pad = 0;       // GSP_TEST_SCALE_LDS_PAD: extra LDS per tick-kernel workgroup
@@ -93,28 +73,6 @@ struct gsp_scale {
     std::vector<Shard> local;  // shards held by this engine (1, or G for an in-process group)
     gsp::DevBuf<gsp::ScaleTickArgs> long_tpl;   // [local][2]: every tile's args by tick parity
                                                 // (scale_long_kernel)
-    std::vector<int32_t> h_fail, h_start;
-    bool joins = false;        // a join schedule is set (some node starts after tick 0)
-    gsp::JoinPlan plan;        // the joiners of every start tick
-    struct Timed { hipEvent_t a, b, c; };
-    std::vector<Timed> pending;
-    std::vector<hipEvent_t> free_events;
-    gsp_scale_perf perf{};
-
-    void recycle(const Timed &t) {     // a tick's three events back to the pool
-        for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
-    }
-
-    hipEvent_t event() {
-        if (!free_events.empty()) {
-            hipEvent_t e = free_events.back();
-            free_events.pop_back();
-            return e;
-        }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
-        return e;
-    }
 
     gsp::ScaleTickArgs args(Shard &sh, int32_t t) const {
         gsp::ScaleTickArgs a{};
@@ -223,38 +181,13 @@ struct gsp_scale {
     }
 };
 
-namespace gsp {
-
-// Failure schedule: the same Philox draws as the oracle (policy.hpp; DESIGN.md "Scale mode").
-std::vector<int32_t> scale_fail_ticks(const gsp_scale_params &p) {
-    return fail_ticks(p.policy, p.n, p.seed, p.fail_mode, p.fail_tick, p.fail_ppm);
-}
+namespace {
 
 int validate_scale_params(const gsp_scale_params *p) {
     GSP_REQUIRE(p, GSP_ERR_INVALID, "scale params NULL");
     GSP_REQUIRE(p->n >= 2 && p->n <= (1 << 21), GSP_ERR_INVALID, "n=%d outside [2, 2^21]", p->n);
-    GSP_REQUIRE(p->fanout >= 1 && p->fanout <= 16, GSP_ERR_INVALID, "fanout=%d outside [1,16]",
-                p->fanout);
-    GSP_REQUIRE(p->tremove >= 1 && p->tremove <= 31, GSP_ERR_INVALID,
-                "tremove=%d outside [1,31] (ts is stored mod 32)", p->tremove);
-    GSP_REQUIRE(p->h0 >= 1 && p->h0 < 2047, GSP_ERR_INVALID, "h0=%d outside [1,2046]", p->h0);
-    GSP_REQUIRE(p->drop_pct >= 0 && p->drop_pct <= 100, GSP_ERR_INVALID, "drop_pct=%d", p->drop_pct);
-    GSP_REQUIRE(p->fail_mode >= 0 && p->fail_mode <= 2, GSP_ERR_INVALID, "fail_mode=%d", p->fail_mode);
-    GSP_REQUIRE(p->tfail == 0 || (p->tfail >= 1 && p->tfail < p->tremove), GSP_ERR_INVALID,
-                "tfail=%d: 0 (off) or 1..tremove-1", p->tfail);
-    GSP_REQUIRE(p->swim >= 0 && p->swim <= 8, GSP_ERR_INVALID, "swim=%d: 0 (off) or 1..8 paths",
-                p->swim);
-    GSP_REQUIRE(p->max_ticks >= 1 && int64_t(p->h0) + p->max_ticks <= 2047, GSP_ERR_RANGE,
-                "h0 + max_ticks = %d exceeds the 11-bit packed heartbeat (2047)",
-                p->h0 + p->max_ticks);
-    GSP_REQUIRE(p->events >= 0 && p->events <= 15, GSP_ERR_INVALID, "events=%d: 0 off, 1 all, or an OR of GSP_EVENTS_*", p->events);
-    GSP_REQUIRE(p->event_cap >= 0, GSP_ERR_INVALID, "event_cap=%lld", (long long)p->event_cap);
-    return validate_policy(p->policy, p->n);
+    return gsp::validate_common(*p);
 }
-
-}  // namespace gsp
-
-namespace {
 
 int shard_alloc(gsp_scale *s, Shard &sh) {
     const int32_t n = s->p.n;
@@ -269,19 +202,6 @@ int shard_alloc(gsp_scale *s, Shard &sh) {
         GSP_HIP(sh.cnt_total[b].alloc(size_t(n)));
         GSP_HIP(hipMemsetAsync(sh.cnt_total[b].p, 0, size_t(n) * 4, st));
     }
-    GSP_HIP(sh.own_hb.alloc(rows));
-    GSP_HIP(sh.fail_tick.alloc(size_t(n)));
-    GSP_HIP(sh.out_dst.alloc(rows * s->p.fanout));
-    if (s->p.swim > 0) {
-        GSP_HIP(sh.ping.alloc(rows));
-        GSP_HIP(hipMemsetAsync(sh.ping.p, 0xFF, rows * 4, st));   // -1: no probe yet
-    }
-    GSP_HIP(sh.deg.alloc(size_t(n)));
-    GSP_HIP(sh.off.alloc(rows + 1));
-    GSP_HIP(sh.fill.alloc(rows));
-    GSP_HIP(sh.csr_src.alloc(size_t(n) * s->p.fanout));
-    GSP_HIP(sh.err.alloc(1));
-    GSP_HIP(sh.tile_sum.alloc(size_t(n) / 4096 + 1));
     if (s->owns_csr(sh)) {
         GSP_HIP(sh.long_list.alloc(2 * (rows + 1)));
         GSP_HIP(hipMemsetAsync(sh.long_list.p, 0, 2 * (rows + 1) * 4, st));
@@ -303,29 +223,13 @@ int shard_alloc(gsp_scale *s, Shard &sh) {
     if (s->rowmode)
         GSP_HIP(sh.x.alloc(s->shards, s->pair_cap, s->msg_cap, int32_t(s->stride / 4), false,
                            s->comm != nullptr, int64_t(n) * s->p.fanout, st));
-    const size_t dig = size_t(s->p.max_ticks + 1) * gsp::kDigSlots * gsp::kDigFields;
-    GSP_HIP(sh.dig.alloc(dig));
-    GSP_HIP(hipMemsetAsync(sh.dig.p, 0, dig * sizeof(unsigned long long), st));
-    if (s->p.events) GSP_HIP(sh.ev.alloc(s->p.events, s->p.event_cap, st));
     if (s->joins) {
-        GSP_HIP(sh.start_tick.alloc(size_t(n)));
-        GSP_HIP(hipMemcpyAsync(sh.start_tick.p, s->h_start.data(), size_t(n) * 4, hipMemcpyHostToDevice, st));
-        const size_t nj = std::max<size_t>(1, s->plan.joiners.size());
-        GSP_HIP(sh.joiners.alloc(nj));
-        GSP_HIP(sh.join_ok.alloc(nj));
-        if (!s->plan.joiners.empty())
-            GSP_HIP(hipMemcpyAsync(sh.joiners.p, s->plan.joiners.data(), s->plan.joiners.size() * 4,
-                                   hipMemcpyHostToDevice, st));
         // a late joiner's row is read (empty) at its start tick from either buffer, and the
         // init kernel skips the rows that have not started
         for (int b = 0; b < 2; ++b) GSP_HIP(hipMemsetAsync(sh.table[b].p, 0, tab * sizeof(uint16_t), st));
         if (s->rowmode && sh.row0 != 0) GSP_HIP(sh.intro_buf.alloc(size_t(s->stride)));
     }
-    GSP_HIP(hipMemsetAsync(sh.own_hb.p, 0, rows * 4, st));
-    GSP_HIP(hipMemsetAsync(sh.deg.p, 0, size_t(n) * 4, st));
-    GSP_HIP(hipMemsetAsync(sh.err.p, 0, 4, st));
-    GSP_HIP(hipMemcpyAsync(sh.fail_tick.p, s->h_fail.data(), size_t(n) * 4, hipMemcpyHostToDevice, st));
-    return GSP_OK;
+    return gsp::shard_alloc_core(*s, sh, size_t(s->p.max_ticks + 1) * gsp::kDigSlots * gsp::kDigFields);
 }
 
 // all-gather of every shard's per-row slice counts into every shard's cnt_all[G][n]
@@ -425,127 +329,11 @@ int exchange_row_counts(gsp_scale *s, int32_t t) {
     return GSP_OK;
 }
 
-// Row layout: the sender rows of tick t_sent's cross-shard messages move to their receivers'
-// shards (rowx_host.cpp); every shard gets the receiver CSR of tick t_sent + 1.
-int exchange_rows(gsp_scale *s, int32_t t_sent) {
-    gsp::RowxJob job{s->p.n, s->shards, s->p.fanout, int32_t(s->stride / 4), false, s->pair_cap,
-                     s->msg_cap, s->comm, s->st, t_sent + 1, &s->rowx};
-    // a joiner's sends ramp up to F over its first ticks (its view grows): the joiners of the
-    // last three send ticks count as new senders
-    job.new_senders = s->joins ? s->plan.count(t_sent) + s->plan.count(t_sent - 1) + s->plan.count(t_sent - 2) : 0;
-    job.drop_now = gsp::drop_at(s->p.policy, s->p.drop_pct, t_sent);
-    job.drop_before = gsp::drop_at(s->p.policy, s->p.drop_pct, t_sent - 1);
-    std::vector<gsp::RowxShard> v;
-    for (Shard &sh : s->local)
-        v.push_back(gsp::RowxShard{sh.g, sh.row0, sh.rows, sh.out_dst.p,
-                                   reinterpret_cast<const uint64_t *>(sh.table[t_sent & 1].p),
-                                   sh.deg.p, sh.off.p, sh.fill.p, sh.csr_src.p, sh.tile_sum.p,
-                                   s->local[0].err.p, &sh.x});
-    return gsp::rowx_exchange(job, v, &s->perf.xgmi_bytes);
-}
-
-// The capacity flag as last mirrored to the host (no synchronisation): a receiver with more
-// than max_segment messages sets the flag to the tick, and every later tick kernel returns at
-// once, so the job's state stays that of the tick before the overflow.  Every shard held by
-// this engine reads one flag (shard 0's); with a communicator the flag is exchanged each tick
-// (columns: inside the picks all-reduce, and every rank holds the same receiver segments; rows:
-// all-reduced ahead of the tick kernels, and again with the exchange counts), so all ranks
-// stop at the same tick and report it from their own flag.  Without a test's bound
-// (GSP_TEST_MAX_SEGMENT) no segment overflows: segments past kMaxSegment are sorted in HBM.
-int mirrored_err(gsp_scale *s) {
-    for (size_t i = 0; i < s->local.size(); ++i)
-    {
-        const int32_t e = s->h_err[i];
-        GSP_REQUIRE(!(e & gsp::kRowxErrBit), GSP_ERR_CAPACITY,
-                    "row exchange at tick %d: a shard's rows or records passed the region capacity "
-                    "or the size posted to RCCL; ticks after it did not run", e & ~gsp::kRowxErrBit);
-        GSP_REQUIRE(e == 0, GSP_ERR_CAPACITY,
-                    "a receiver got more than %d messages at tick %d; ticks after it did not run",
-                    s->max_segment, e);
-    }
-    return GSP_OK;
-}
-
-int check_err(gsp_scale *s) {
-    for (size_t i = 0; i < s->local.size(); ++i)
-        GSP_HIP(hipMemcpyAsync(s->h_err + i, s->local[i].err.p, 4, hipMemcpyDeviceToHost, s->st));
-    GSP_HIP(hipStreamSynchronize(s->st));
-    return mirrored_err(s);
-}
-
-// The JOINREPs node 0 sends at tick t to the nodes that start at t + 1 (join_kernels.hpp):
-// deg of the receivers (next tick's CSR) and the digest's sent / dropped of tick t; the row
-// layout also broadcasts node 0's row of tick t to the other shards (the JOINREP payload).
-int join_sends(gsp_scale *s, int32_t t) {
-    const int64_t cnt = s->plan.count(t + 1);
-    if (!s->joins || cnt == 0) return GSP_OK;
-    for (Shard &sh : s->local) {
-        if (!s->owns_csr(sh)) continue;   // one CSR (shard 0's deg)
-        gsp::JoinSendArgs j{};
-        j.joiners = sh.joiners.p + s->plan.first(t + 1);
-        j.count = int32_t(cnt);
-        j.tick = t;
-        j.drop_pct = gsp::drop_at(s->p.policy, s->p.drop_pct, t);
-        j.seed = s->p.seed;
-        j.fail_tick = sh.fail_tick.p;
-        j.lo = s->rowmode ? sh.row0 : 0;
-        j.hi = s->rowmode ? sh.row0 + sh.rows : s->p.n;
-        j.ok = sh.join_ok.p + s->plan.first(t + 1);
-        j.deg = sh.deg.p;
-        const bool counts = s->rowmode || sh.g == 0;
-        unsigned long long *dig = sh.dig.p + size_t(t) * gsp::kDigSlots * gsp::kDigFields;
-        j.sent = counts ? dig + gsp::kDigSent : nullptr;
-        j.dropped = counts ? dig + gsp::kDigDropped : nullptr;
-        GSP_HIP(gsp::launch_join_send(j, s->st));
-    }
-    if (!s->rowmode || s->shards == 1) return GSP_OK;
-    // node 0's row of tick t -> intro_buf of every other shard
-    const size_t bytes = size_t(s->stride) * sizeof(uint16_t);
-    if (s->comm) {
-        Shard &sh = s->local[0];
-        void *buf = sh.row0 == 0 ? static_cast<void *>(sh.table[t & 1].p) : static_cast<void *>(sh.intro_buf.p);
-        GSP_NCCL(ncclBroadcast(buf, buf, bytes, ncclUint8, 0, s->comm, s->st));
-        s->perf.xgmi_bytes += sh.row0 == 0 ? double(bytes) * double(s->shards - 1) : 0.0;
-        return GSP_OK;
-    }
-    const Shard &root = s->local[0];
-    for (Shard &sh : s->local)
-        if (sh.row0 != 0) {
-            GSP_HIP(hipMemcpyAsync(sh.intro_buf.p, root.table[t & 1].p, bytes, hipMemcpyDeviceToDevice, s->st));
-            s->perf.xgmi_bytes += double(bytes);
-        }
-    return GSP_OK;
-}
-
-// the delivered JOINREPs of tick t into every local shard's receiver CSR (after the scan)
-int join_scatter(gsp_scale *s, int32_t t) {
-    const int64_t cnt = s->plan.count(t);
-    if (!s->joins || cnt == 0) return GSP_OK;
-    for (Shard &sh : s->local) {
-        if (!s->owns_csr(sh)) continue;
-        GSP_HIP(gsp::launch_join_scatter(sh.joiners.p + s->plan.first(t), sh.join_ok.p + s->plan.first(t),
-                                         int32_t(cnt), s->rowmode ? sh.row0 : 0,
-                                         s->rowmode ? sh.rows : s->p.n, sh.off.p, sh.fill.p, sh.csr_src.p,
-                                         s->rowmode ? sh.x.csr_slot.p : nullptr, s->st));
-    }
-    return GSP_OK;
-}
-
-int collect_timing(gsp_scale *s) {
-    for (auto &t : s->pending) {
-        float a = 0.f, b = 0.f;
-        GSP_HIP(hipEventSynchronize(t.c));
-        GSP_HIP(hipEventElapsedTime(&a, t.a, t.b));
-        GSP_HIP(hipEventElapsedTime(&b, t.b, t.c));
-        s->perf.csr_ms += a;
-        s->perf.merge_ms += b;
-        s->perf.merge_launches++;
-        s->recycle(t);
-    }
-    s->pending.clear();
-    if (s->rowmode)
-        if (int rc = gsp::rowx_collect(s->rowx, &s->perf.xgmi_bytes)) return rc;
-    return GSP_OK;
+// JOINREPs (engine_host.hpp): one CSR for shared column tiles; per-row digest counters are
+// shard 0's outside the row layout; the payload is node 0's row
+gsp::JoinForm join_form(const gsp_scale *s) {
+    return {s->shared, s->rowmode, size_t(gsp::kDigSlots) * gsp::kDigFields, gsp::kDigSent,
+            gsp::kDigDropped, size_t(s->stride) * sizeof(uint16_t)};
 }
 
 // scale_long_kernel's tile table: each tile's args at both tick parities (digest base at tick
@@ -596,18 +384,12 @@ int scale_build(const gsp_scale_params *p, int device, int32_t shards, int32_t r
                 int32_t local_shards, const void *nccl_id, int32_t layout, gsp_scale **out) {
     GSP_REQUIRE(out, GSP_ERR_INVALID, "gsp_scale: out is NULL");
     *out = nullptr;
-    if (int rc = gsp::validate_scale_params(p)) return rc;
+    if (int rc = validate_scale_params(p)) return rc;
     GSP_REQUIRE(shards >= 1 && shards <= 64 && rank >= 0 && rank + local_shards <= shards,
                 GSP_ERR_INVALID, "gsp_scale: shards=%d rank=%d", shards, rank);
-    int ndev = 0;
-    GSP_HIP(hipGetDeviceCount(&ndev));
-    GSP_REQUIRE(device >= 0 && device < ndev, GSP_ERR_HIP, "gsp_scale: device %d of %d", device, ndev);
-    GSP_HIP(hipSetDevice(device));
     std::unique_ptr<gsp_scale> s(new gsp_scale);
     s->p = *p;
-    s->device = device;
-    s->shards = shards;
-    s->rank = rank;
+    if (int rc = gsp::engine_begin(*s, "gsp_scale", device, shards, rank)) return rc;
     GSP_REQUIRE(layout == GSP_SHARD_COLUMNS || layout == GSP_SHARD_ROWS, GSP_ERR_INVALID,
                 "gsp_scale: layout %d", layout);
     GSP_REQUIRE(shards <= p->n, GSP_ERR_INVALID, "gsp_scale: %d shards for %d nodes", shards, p->n);
@@ -638,10 +420,6 @@ int scale_build(const gsp_scale_params *p, int device, int32_t shards, int32_t r
         s->msg_cap = std::min<int64_t>(int64_t(rows_max) * p->fanout,
                                        int64_t(double(rows_max) * p->fanout / shards * 1.25) + 4096);
     }
-    s->h_fail = gsp::scale_fail_ticks(*p);
-    s->h_start = gsp::start_ticks(p->policy, p->n);
-    s->joins = p->policy.step_rate > 0 && *std::max_element(s->h_start.begin(), s->h_start.end()) > 0;
-    if (s->joins) s->plan = gsp::join_plan(s->h_start, p->max_ticks + 1);
     if (const char *pol = std::getenv("GSP_TEST_SCALE_POLICY")) s->policy = std::atoi(pol) & 7;
     if (const char *pad = std::getenv("GSP_TEST_SCALE_LDS_PAD")) s->lds_pad = std::max(0, std::min(65536, std::atoi(pad)));
     if (const char *m = std::getenv("GSP_TEST_SCALE_MERGE")) s->merge = std::atoi(m) ? 1 : 0;
@@ -655,17 +433,8 @@ int scale_build(const gsp_scale_params *p, int device, int32_t shards, int32_t r
     if (const char *ms = std::getenv("GSP_TEST_MAX_SEGMENT"))   // tests only: force overflows
         s->max_segment = std::max(1, std::atoi(ms));
     s->sweep = sweep_width(*s);
-    GSP_HIP(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-    GSP_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_err), size_t(local_shards) * 4));
-    std::memset(s->h_err, 0, size_t(local_shards) * 4);
-    if (s->rowmode) {
-        GSP_HIP(s->rowx.init(shards, nccl_id != nullptr));
-    }
-    if (nccl_id) {
-        ncclUniqueId id;
-        std::memcpy(&id, nccl_id, sizeof id);
-        GSP_NCCL(ncclCommInitRank(&s->comm, shards / local_shards, id, rank / local_shards));
-    }
+    if (int rc = gsp::engine_open(*s, local_shards, nccl_id, shards / local_shards, rank / local_shards))
+        return rc;
     s->local.resize(size_t(local_shards));
     for (int32_t i = 0; i < local_shards; ++i) {
         Shard &sh = s->local[size_t(i)];
@@ -681,7 +450,7 @@ int scale_build(const gsp_scale_params *p, int device, int32_t shards, int32_t r
         if (int rc = resolve_sends(s.get(), 0)) return rc;
     if (s->rowmode)
         if (int rc = exchange_row_counts(s.get(), 0)) return rc;
-    if (int rc = join_sends(s.get(), 0)) return rc;
+    if (int rc = gsp::join_sends(s.get(), 0, join_form(s.get()))) return rc;
     GSP_HIP(hipStreamSynchronize(s->st));
     *out = s.release();
     return GSP_OK;
@@ -737,14 +506,9 @@ int gsp_scale_destroy(gsp_scale *s) {
     if (!s) return GSP_OK;
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
-    for (auto &t : s->pending) s->recycle(t);
-    for (hipEvent_t e : s->free_events) (void)hipEventDestroy(e);
     for (Shard &sh : s->local) sh.release();
     s->long_tpl.release();
-    if (s->comm) (void)ncclCommDestroy(s->comm);
-    s->rowx.release();
-    if (s->h_err) (void)hipHostFree(s->h_err);
-    if (s->st) (void)hipStreamDestroy(s->st);
+    gsp::engine_close(*s);
     delete s;
     return GSP_OK;
 }
@@ -760,9 +524,7 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
     // no row, the row exchange returns the error on every rank at the same tick, and sync
     // reports it
     if (!s->comm)
-        if (int rc = mirrored_err(s)) return rc;
-    const int32_t n = s->p.n;
-    const int64_t slots = int64_t(n) * s->p.fanout;
+        if (int rc = gsp::mirrored_err(s, 0)) return rc;
     for (int32_t i = 0; i < ticks; ++i) {
         const int32_t t = s->tick + 1;
         gsp_scale::Timed tm{};
@@ -771,7 +533,7 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
             GSP_HIP(hipEventRecord(tm.a, s->st));
         }
         if (s->rowmode) {
-            if (int rc = exchange_rows(s, t - 1)) return rc;
+            if (int rc = gsp::exchange_rows(s, t - 1, int32_t(s->stride / 4), false)) return rc;
             // ranks (row shards): a segment past a test's bound stops every rank's tick t, not
             // only the holder's -- the flag is checked ahead of the tick kernel and all-reduced
             // (ADVICE r03); unbounded otherwise (long segments are sorted in HBM)
@@ -783,14 +545,10 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
         } else {
             for (Shard &sh : s->local) {
                 if (!s->owns_csr(sh)) continue;   // one CSR for every shard
-                GSP_HIP(gsp::launch_exclusive_scan(sh.deg.p, sh.off.p, n, sh.tile_sum.p, s->st));
-                GSP_HIP(hipMemsetAsync(sh.fill.p, 0, size_t(n) * 4, s->st));
-                GSP_HIP(gsp::launch_scatter(sh.out_dst.p, slots, s->p.fanout, 0, sh.off.p, sh.fill.p,
-                                            sh.csr_src.p, s->st));
-                GSP_HIP(hipMemsetAsync(sh.deg.p, 0, size_t(n) * 4, s->st));
+                if (int rc = gsp::csr_build(sh, s->p.n, s->p.fanout, s->st)) return rc;
             }
         }
-        if (int rc = join_scatter(s, t)) return rc;
+        if (int rc = gsp::join_scatter(s, t, s->shared)) return rc;
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
         for (Shard &sh : s->local)
             GSP_HIP(gsp::launch_scale_tick(s->args(sh, t), s->sliced, s->merge, s->st));
@@ -810,21 +568,19 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
             if (int rc = resolve_sends(s, t)) return rc;
         if (s->rowmode)
             if (int rc = exchange_row_counts(s, t)) return rc;
-        if (int rc = join_sends(s, t)) return rc;
+        if (int rc = gsp::join_sends(s, t, join_form(s))) return rc;
         s->tick = t;
         s->perf.ticks++;
     }
-    for (size_t i = 0; i < s->local.size(); ++i)     // read by the next call, never waited on
-        GSP_HIP(hipMemcpyAsync(s->h_err + i, s->local[i].err.p, 4, hipMemcpyDeviceToHost, s->st));
-    return GSP_OK;
+    return gsp::mirror_err(s);
 }
 
 int gsp_scale_sync(gsp_scale *s) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_sync: NULL");
     GSP_HIP(hipSetDevice(s->device));
     GSP_HIP(hipStreamSynchronize(s->st));
-    if (int rc = collect_timing(s)) return rc;
-    return check_err(s);
+    if (int rc = gsp::collect_timing(*s)) return rc;
+    return gsp::check_err(s, 0);       // 0: the full view sets no drain-all bit
 }
 
 int gsp_scale_tick(gsp_scale *s, int32_t *tick) {
@@ -841,13 +597,7 @@ int gsp_scale_digest_get(gsp_scale *s, int32_t t, gsp_scale_digest *out) {
     GSP_REQUIRE(t >= 0 && t <= s->tick, GSP_ERR_INVALID, "gsp_scale_digest_get: tick %d", t);
     if (int rc = gsp_scale_sync(s)) return rc;
     unsigned long long f[gsp::kDigFields] = {0};
-    std::vector<unsigned long long> h(size_t(gsp::kDigSlots) * gsp::kDigFields);
-    for (Shard &sh : s->local) {
-        GSP_HIP(hipMemcpy(h.data(), sh.dig.p + size_t(t) * h.size(), h.size() * 8,
-                          hipMemcpyDeviceToHost));
-        for (int sl = 0; sl < gsp::kDigSlots; ++sl)
-            for (int k = 0; k < gsp::kDigFields; ++k) f[k] += h[size_t(sl) * gsp::kDigFields + k];
-    }
+    if (int rc = gsp::digest_sum(*s, t, gsp::kDigSlots, gsp::kDigFields, f)) return rc;
     out->tick = t;
     out->node_rounds = int64_t(f[gsp::kDigRounds]);
     out->merges = int64_t(f[gsp::kDigMerges]);
@@ -870,13 +620,11 @@ int gsp_scale_row(gsp_scale *s, int32_t r, uint16_t *buf, int32_t cap) {
     // a crashed row stops at its fail tick: read the buffer of the last tick it ran
     const int32_t last = std::min(s->tick, s->h_fail[size_t(r)]);
     if (s->rowmode) {
-        for (Shard &sh : s->local)
-            if (r >= sh.row0 && r < sh.row0 + sh.rows) {
-                GSP_HIP(hipMemcpy(buf, sh.table[last & 1].p + size_t(r - sh.row0) * size_t(s->stride),
-                                  size_t(s->p.n) * 2, hipMemcpyDeviceToHost));
-                return GSP_OK;
-            }
-        GSP_REQUIRE(false, GSP_ERR_INVALID, "gsp_scale_row: row %d is not held by this rank", r);
+        Shard *sh = gsp::holder(*s, r);
+        GSP_REQUIRE(sh, GSP_ERR_INVALID, "gsp_scale_row: row %d is not held by this rank", r);
+        GSP_HIP(hipMemcpy(buf, sh->table[last & 1].p + size_t(r - sh->row0) * size_t(s->stride),
+                          size_t(s->p.n) * 2, hipMemcpyDeviceToHost));
+        return GSP_OK;
     }
     for (Shard &sh : s->local) {
         const int64_t c0 = sh.col0;
@@ -891,36 +639,15 @@ int gsp_scale_row(gsp_scale *s, int32_t r, uint16_t *buf, int32_t cap) {
 int gsp_scale_own_hb(gsp_scale *s, int32_t r, int32_t *hb) {
     GSP_REQUIRE(s && hb && r >= 0 && r < s->p.n, GSP_ERR_INVALID, "gsp_scale_own_hb: bad row");
     if (int rc = gsp_scale_sync(s)) return rc;
-    for (Shard &sh : s->local)
-        if (r >= sh.row0 && r < sh.row0 + sh.rows) {
-            GSP_HIP(hipMemcpy(hb, sh.own_hb.p + (r - sh.row0), 4, hipMemcpyDeviceToHost));
-            return GSP_OK;
-        }
-    GSP_REQUIRE(false, GSP_ERR_INVALID, "gsp_scale_own_hb: row %d is not held by this rank", r);
-    return GSP_OK;
+    return gsp::read_own_hb(*s, "gsp_scale_own_hb", r, hb);
 }
 
 int gsp_scale_messages(gsp_scale *s, int32_t *dst, int64_t cap, int64_t *n) {
     GSP_REQUIRE(s && n, GSP_ERR_INVALID, "gsp_scale_messages: NULL");
     if (int rc = gsp_scale_sync(s)) return rc;
-    if (!s->rowmode) {
-        const int64_t slots = int64_t(s->p.n) * s->p.fanout;
-        *n = slots;
-        if (dst && cap > 0)
-            GSP_HIP(hipMemcpy(dst, s->local[0].out_dst.p, size_t(std::min(cap, slots)) * 4,
-                              hipMemcpyDeviceToHost));
-        return GSP_OK;
-    }
-    int64_t total = 0;          // row layout: the slots of the rows held here, in row order
-    for (Shard &sh : s->local) {
-        const int64_t slots = int64_t(sh.rows) * s->p.fanout;
-        if (dst && total < cap)
-            GSP_HIP(hipMemcpy(dst + total, sh.out_dst.p, size_t(std::min(cap - total, slots)) * 4,
-                              hipMemcpyDeviceToHost));
-        total += slots;
-    }
-    *n = total;
-    return GSP_OK;
+    // row layout: the slots of the rows held here; else every local shard holds all n rows and
+    // local[0]'s out_dst is the job's n * fanout slots
+    return gsp::read_messages(*s, s->rowmode ? s->local.size() : 1, dst, cap, n);
 }
 
 int gsp_scale_perf_get(gsp_scale *s, gsp_scale_perf *out) {
@@ -971,11 +698,7 @@ int gsp_scale_drain_events(gsp_scale *s, uint64_t *buf, int64_t cap, int64_t *n,
     GSP_REQUIRE(s->p.events, GSP_ERR_INVALID, "gsp_scale_drain_events: the engine records no events "
                 "(gsp_scale_params.events = 0)");
     if (int rc = gsp_scale_sync(s)) return rc;
-    int64_t total = 0, dropped = 0;
-    for (Shard &sh : s->local) GSP_HIP(sh.ev.drain(buf, cap, &total, &dropped));
-    *n = total;
-    if (lost) *lost = dropped;
-    return GSP_OK;
+    return gsp::drain_events(*s, buf, cap, n, lost);
 }
 
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {

@@ -111,6 +111,46 @@ def test_scale_variant_params_validated_before_the_device():
             assert L.gsp_scale_create(ctypes.byref(sp), 0, ctypes.byref(h)) not in (0, -1), ok
 
 
+def test_engine_params_out_of_range_status_and_message():
+    """Every out-of-range parameter of gsp_scale_create and gsp_pview_create fails before any HIP
+    call with its exact status (max_ticks: GSP_ERR_RANGE, everything else: GSP_ERR_INVALID) and
+    a gsp_last_error() that names the field; the last accepted n gets past validation."""
+    L = _lib.lib()
+    hdr = open(os.path.join(ROOT, "include/gossip/gossip.h")).read()
+    invalid = int(re.search(r"GSP_ERR_INVALID\s*=\s*(-?\d+)", hdr).group(1))
+    rng = int(re.search(r"GSP_ERR_RANGE\s*=\s*(-?\d+)", hdr).group(1))
+    assert invalid == -1
+    h = ctypes.c_void_p()
+    common = [(dict(h0=48, max_ticks=2000), rng, "max_ticks"), (dict(max_ticks=0), rng, "max_ticks"),
+              (dict(fanout=0), invalid, "fanout"), (dict(fanout=17), invalid, "fanout"),
+              (dict(tremove=0), invalid, "tremove"), (dict(tremove=32), invalid, "tremove"),
+              (dict(h0=0), invalid, "h0"), (dict(h0=2047), invalid, "h0"),
+              (dict(drop_pct=-1), invalid, "drop_pct"), (dict(drop_pct=101), invalid, "drop_pct"),
+              (dict(fail_mode=3), invalid, "fail_mode"), (dict(tfail=20), invalid, "tfail"),
+              (dict(swim=9), invalid, "swim"), (dict(events=16), invalid, "events"),
+              (dict(event_cap=-1), invalid, "event_cap"), (dict(n=1), invalid, "n")]
+    scale_base = dict(n=1024, fanout=3, tremove=20, h0=1, max_ticks=16)
+    pview_base = dict(scale_base, view=64, inbox=7)
+    engines = [
+        (L.gsp_scale_create, _lib.GspScaleParams, scale_base,
+         common + [(dict(n=2**21 + 1), invalid, "n")], dict(n=2**21)),
+        (L.gsp_pview_create, _lib.GspPviewParams, pview_base,
+         common + [(dict(n=2**21), invalid, "n"), (dict(inbox=0, n=2**21 - 767), invalid, "n"),
+                   (dict(view=0), invalid, "view"), (dict(view=257), invalid, "view"),
+                   (dict(inbox=8), invalid, "inbox"), (dict(evict_order=2), invalid, "evict_order")],
+         dict(n=2**21 - 1)),
+    ]
+    for create, Params, base, cases, last_ok in engines:
+        for bad, status, field in cases:
+            p = Params(**dict(base, **bad))
+            assert create(ctypes.byref(p), 0, ctypes.byref(h)) == status, bad
+            msg = L.gsp_last_error().decode()
+            assert msg and re.search(r"\b%s\b" % field, msg), (bad, msg)
+        if L.gsp_device_count() == 0:
+            p = Params(**dict(base, **last_ok))
+            assert create(ctypes.byref(p), 0, ctypes.byref(h)) not in (0, invalid, rng), last_ok
+
+
 def test_struct_layouts_match_the_header():
     """Every public struct the ctypes stub mirrors has the C ABI's size."""
     L = _lib.lib()

@@ -116,8 +116,18 @@ class GspPviewDigest(ctypes.Structure):
                 ("evicts", c_int64), ("event_hash", c_uint64)]
 
 
+class GspCensusInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("alive", c_int32),
+                ("entries", c_int64), ("kernel_ms", ctypes.c_double)]
+
+
+_CENSUS = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(ctypes.c_uint32), P(ctypes.c_uint32),
+                          P(ctypes.c_uint32), P(ctypes.c_uint8), P(GspCensusInfo)])
+
 # name -> (restype, argtypes); every name here must be exported (tests check it)
 SIGNATURES = {
+    "gsp_scale_census": _CENSUS,
+    "gsp_pview_census": _CENSUS,
     "gsp_last_error": (ctypes.c_char_p, []),
     "gsp_abi_version": (ctypes.c_int, []),
     "gsp_device_count": (ctypes.c_int, []),

@@ -5,8 +5,9 @@
 // plus their own tables each); the function templates below take the engine type E and read
 // only those members.  Here: the stream, the timing-event pool, the failure / join schedule,
 // the communicator, the capacity flag and its host mirror, the single-shard CSR build, the
-// JOINREP sends, the call into the row exchange (rowx_host.hpp) and the C-ABI bodies that are
-// the same code.  Tables, tick arguments, kernels launched and test knobs stay with each engine.
+// JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census
+// and the C-ABI bodies that are the same code.  Tables, tick arguments, kernels launched and
+// test knobs stay with each engine.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -14,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "census_kernels.hpp"
 #include "common.hpp"
 #include "event_ring.hpp"
 #include "join_kernels.hpp"
@@ -42,6 +44,25 @@ struct ShardCore {
     }
 };
 
+// The census accumulators (gsp_scale_census / gsp_pview_census), allocated by the first call:
+// n-length device arrays and their host staging; the full view counts into listed / fresh, the
+// partial view into counts (fresh << 32 | listed, split at readback).
+struct CensusBufs {
+    DevBuf<uint32_t> listed, fresh, max_hb;
+    DevBuf<unsigned long long> counts;
+    std::vector<uint32_t> h32;
+    std::vector<unsigned long long> h64;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+
+    void release() {
+        for (auto *b : {&listed, &fresh, &max_hb}) b->release();
+        counts.release();
+        for (hipEvent_t e : {t0, t1})
+            if (e) (void)hipEventDestroy(e);
+        t0 = t1 = nullptr;
+    }
+};
+
 struct EngineCore {
     int device = 0;
     hipStream_t st = nullptr;
@@ -63,6 +84,7 @@ struct EngineCore {
     std::vector<Timed> pending;
     std::vector<hipEvent_t> free_events;
     gsp_scale_perf perf{};
+    CensusBufs census;
 
     void recycle(const Timed &t) {     // a tick's three events back to the pool
         for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
@@ -139,6 +161,7 @@ inline void engine_close(EngineCore &c) {
     for (auto &t : c.pending) c.recycle(t);
     for (hipEvent_t e : c.free_events) (void)hipEventDestroy(e);
     if (c.comm) (void)ncclCommDestroy(c.comm);
+    c.census.release();
     c.rowx.release();
     if (c.h_err) (void)hipHostFree(c.h_err);
     if (c.st) (void)hipStreamDestroy(c.st);
@@ -393,6 +416,78 @@ int digest_sum(E &s, int32_t t, int slots, int fields, unsigned long long *f) {
     for (auto &sh : s.local) {
         GSP_HIP(hipMemcpy(h.data(), sh.dig.p + size_t(t) * h.size(), h.size() * 8, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < h.size(); ++i) f[i % size_t(fields)] += h[i];
+    }
+    return GSP_OK;
+}
+
+// The census of the engine's current tick T (gossip.h, census_kernels.hpp), after the engine
+// has synchronised and reported any pending capacity error.  `packed`: the engine's kernels
+// count into census.counts (partial view) instead of listed / fresh.  launch(shard) adds that
+// shard's share -- its rows, its columns -- to the zeroed arrays; with a communicator the
+// arrays are then all-reduced on the engine's stream (SUM; MAX for max_hb), so every rank must
+// make the call at the same tick.
+template <class E, class Launch>
+int census_run(E &s, bool packed, int32_t age_limit, uint32_t *listed,
+               uint32_t *fresh, uint32_t *max_hb, uint8_t *state, gsp_census_info *info,
+               Launch launch) {
+    const size_t n = size_t(s.p.n);
+    const int32_t T = s.tick;
+    CensusBufs &c = s.census;
+    if (!c.t1) {                       // first call (t1 is made last: a failed attempt starts over)
+        GSP_HIP(c.max_hb.alloc(n));
+        if (packed) GSP_HIP(c.counts.alloc(n));
+        else {
+            GSP_HIP(c.listed.alloc(n));
+            GSP_HIP(c.fresh.alloc(n));
+        }
+        if (!c.t0) GSP_HIP(hipEventCreate(&c.t0));
+        GSP_HIP(hipEventCreate(&c.t1));
+    }
+    c.h32.resize(packed ? n : 3 * n);
+    c.h64.resize(packed ? n : 0);
+    GSP_HIP(hipMemsetAsync(c.max_hb.p, 0, n * 4, s.st));
+    if (packed) GSP_HIP(hipMemsetAsync(c.counts.p, 0, n * 8, s.st));
+    else {
+        GSP_HIP(hipMemsetAsync(c.listed.p, 0, n * 4, s.st));
+        GSP_HIP(hipMemsetAsync(c.fresh.p, 0, n * 4, s.st));
+    }
+    if (s.timing) GSP_HIP(hipEventRecord(c.t0, s.st));
+    for (auto &sh : s.local)
+        if (int rc = launch(sh)) return rc;
+    if (s.timing) GSP_HIP(hipEventRecord(c.t1, s.st));
+    if (s.comm) {
+        if (packed) GSP_NCCL(ncclAllReduce(c.counts.p, c.counts.p, n, ncclUint64, ncclSum, s.comm, s.st));
+        else {
+            GSP_NCCL(ncclAllReduce(c.listed.p, c.listed.p, n, ncclUint32, ncclSum, s.comm, s.st));
+            GSP_NCCL(ncclAllReduce(c.fresh.p, c.fresh.p, n, ncclUint32, ncclSum, s.comm, s.st));
+        }
+        GSP_NCCL(ncclAllReduce(c.max_hb.p, c.max_hb.p, n, ncclUint32, ncclMax, s.comm, s.st));
+    }
+    uint32_t *h_hb = c.h32.data();
+    GSP_HIP(hipMemcpyAsync(h_hb, c.max_hb.p, n * 4, hipMemcpyDeviceToHost, s.st));
+    if (packed) GSP_HIP(hipMemcpyAsync(c.h64.data(), c.counts.p, n * 8, hipMemcpyDeviceToHost, s.st));
+    else {
+        GSP_HIP(hipMemcpyAsync(h_hb + n, c.listed.p, n * 4, hipMemcpyDeviceToHost, s.st));
+        GSP_HIP(hipMemcpyAsync(h_hb + 2 * n, c.fresh.p, n * 4, hipMemcpyDeviceToHost, s.st));
+    }
+    GSP_HIP(hipStreamSynchronize(s.st));
+    int64_t entries = 0;
+    int32_t alive = 0;
+    for (size_t x = 0; x < n; ++x) {
+        const uint32_t l = packed ? uint32_t(c.h64[x]) : h_hb[n + x];
+        const uint32_t f = packed ? uint32_t(c.h64[x] >> 32) : h_hb[2 * n + x];
+        const uint8_t st = T < s.h_start[x] ? 0 : T <= s.h_fail[x] ? 1 : 2;
+        entries += l;
+        alive += st == 1;
+        if (listed) listed[x] = l;
+        if (fresh) fresh[x] = f;
+        if (max_hb) max_hb[x] = h_hb[x];
+        if (state) state[x] = st;
+    }
+    if (info) {
+        float ms = 0.f;
+        if (s.timing) GSP_HIP(hipEventElapsedTime(&ms, c.t0, c.t1));
+        *info = gsp_census_info{T, s.p.n, age_limit, alive, entries, double(ms)};
     }
     return GSP_OK;
 }

@@ -589,6 +589,35 @@ int gsp_pview_drain_stats(gsp_pview *s, int32_t classes, int64_t *rows, int64_t 
     return GSP_OK;
 }
 
+// Census of the current tick (engine_host.hpp census_run): every local shard adds its rows.
+// GSP_TEST_PV_CENSUS=0|1 (tests, A/B) selects the plain / the LDS-privatised kernel form.
+int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
+                     uint32_t *max_hb, uint8_t *state, gsp_census_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_census: NULL");
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
+                "gsp_pview_census: age_limit=%d outside [1,32]", age_limit);
+    if (int rc = gsp_pview_sync(s)) return rc;
+    bool lds = gsp::kCensusPviewLds;
+    if (const char *f = std::getenv("GSP_TEST_PV_CENSUS")) lds = std::atoi(f) != 0;
+    return gsp::census_run(*s, true, age_limit, listed, fresh, max_hb, state, info, [&](PvShard &sh) -> int {
+        gsp::CensusPviewArgs a{};
+        a.table = sh.table[s->tick & 1].p;
+        a.len = sh.len[s->tick & 1].p;
+        a.n = s->p.n;
+        a.view = s->p.view;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        a.tick = s->tick;
+        a.age_limit = age_limit;
+        a.fail_tick = sh.fail_tick.p;
+        a.start_tick = s->joins ? sh.start_tick.p : nullptr;
+        a.counts = s->census.counts.p;
+        a.max_hb = s->census.max_hb.p;
+        GSP_HIP(gsp::launch_census_pview(a, lds, s->cus, s->st));
+        return GSP_OK;
+    });
+}
+
 int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out) {
     GSP_REQUIRE(s && out, GSP_ERR_INVALID, "gsp_pview_perf_get: NULL");
     if (int rc = gsp_pview_sync(s)) return rc;

@@ -701,6 +701,34 @@ int gsp_scale_drain_events(gsp_scale *s, uint64_t *buf, int64_t cap, int64_t *n,
     return gsp::drain_events(*s, buf, cap, n, lost);
 }
 
+// Census of the current tick (engine_host.hpp census_run): every local shard adds its rows x
+// columns -- the fused table, a column tile from col0, a row shard from row0.
+int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
+                     uint32_t *max_hb, uint8_t *state, gsp_census_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_census: NULL");
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
+                "gsp_scale_census: age_limit=%d outside [1,32]", age_limit);
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::census_run(*s, false, age_limit, listed, fresh, max_hb, state, info, [&](Shard &sh) -> int {
+        gsp::CensusScaleArgs a{};
+        a.table = sh.table[s->tick & 1].p;
+        a.stride = s->stride;
+        a.n = s->p.n;
+        a.col0 = sh.col0;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        a.tick = s->tick;
+        a.age_limit = age_limit;
+        a.fail_tick = sh.fail_tick.p;
+        a.start_tick = s->joins ? sh.start_tick.p : nullptr;
+        a.listed = s->census.listed.p;
+        a.fresh = s->census.fresh.p;
+        a.max_hb = s->census.max_hb.p;
+        GSP_HIP(gsp::launch_census_scale(a, s->st));
+        return GSP_OK;
+    });
+}
+
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {
     GSP_REQUIRE(s && stream, GSP_ERR_INVALID, "gsp_scale_hip_stream: NULL");
     *stream = reinterpret_cast<void *>(s->st);

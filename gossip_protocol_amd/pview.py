@@ -108,6 +108,14 @@ class PviewEngine:
                                        n.value, ctypes.byref(n)), "gsp_pview_messages")
         return buf[:n.value].reshape(-1, self.fanout)
 
+    def census(self, age_limit=None):
+        """The membership census of the current tick (census.Census); age_limit (1..32) bounds
+        `fresh`, default tfail if set, else tremove.  Collective across the ranks of a job."""
+        from . import census
+        if age_limit is None:
+            age_limit = census.default_age_limit(self.params)
+        return census.run(lib().gsp_pview_census, self._h, self.n, age_limit, "gsp_pview_census")
+
     def drain_events(self):
         """(records, lost) since the last drain (events=True); see _lib.split_events."""
         return _lib.drain_events(lib().gsp_pview_drain_events, self._h)

@@ -460,6 +460,35 @@ int gsp_scale_set_merge(gsp_scale *s, int32_t packed);
 int gsp_scale_hip_stream(gsp_scale *s, void **stream);
 
 /* ------------------------------------------------------------------------------------
+ * Membership census: the Grader's questions (did everyone join, was every crashed node removed
+ * by everyone, was no live node removed) asked of the tables in HBM at the engine's current tick
+ * T -- every tick submitted so far; valid at T = 0.  One streaming pass per call, no events
+ * needed, nothing added to create or step.  A row r is alive at T iff start[r] <= T <= crash[r];
+ * rows that are not alive are skipped (a crashed row's buffer is stale).  For every member x,
+ * buffers of n elements each, any of them NULL:
+ *   listed[x]   alive rows whose list holds x (entries as stored: no row lists itself)
+ *   fresh[x]    the same, counting only entries with (T - ts) mod 32 < age_limit (1..32; 32:
+ *               fresh == listed)
+ *   max_hb[x]   the largest heartbeat those rows store for x (0 when listed[x] is 0)
+ *   state[x]    0 not started yet, 1 alive at T, 2 crashed: the engine's own schedule
+ * The arrays are the same for every layout and number of shards.  With a communicator
+ * (gsp_*_create_rank*) the call is COLLECTIVE: each rank counts the rows and columns it holds
+ * and the arrays are all-reduced on the engine's stream, so every rank must make the call at
+ * the same tick, and every rank gets the whole result.  A pending capacity error returns
+ * GSP_ERR_CAPACITY as the other reads do.  The accumulators (12 B per node) are allocated by
+ * the first call and freed at destroy.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t tick, n, age_limit;
+    int32_t alive;        /* nodes with state 1                                   */
+    int64_t entries;      /* sum of listed[]                                      */
+    double kernel_ms;     /* HIP events around the census kernels (0: timing off) */
+} gsp_census_info;
+
+int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
+                     uint32_t *max_hb, uint8_t *state, gsp_census_info *info);
+
+/* ------------------------------------------------------------------------------------
  * Event stream (params.events != 0): the tick kernels append every join / remove (partial
  * view: and evict) of the selected kinds as one 64-bit record kind << 62 | t << 42 | r << 21
  * | x (kind 1 join, 2 remove, 3 evict; r = the node whose list changed, x = the member) --
@@ -543,6 +572,9 @@ int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out);
  * entries (class c < 4: the LDS classes, 4: the hub kernel; entries past them 0).  The
  * counts are read back with the split kernels' bucket sizes (the default launch form). */
 int gsp_pview_drain_stats(gsp_pview *s, int32_t classes, int64_t *rows, int64_t *messages, double *ms);
+/* As gsp_scale_census ("Membership census" above), over the views. */
+int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
+                     uint32_t *max_hb, uint8_t *state, gsp_census_info *info);
 /* As gsp_scale_drain_events (join / remove / evict records). */
 int gsp_pview_drain_events(gsp_pview *s, uint64_t *buf, int64_t cap, int64_t *n, int64_t *lost);
 /* Test diagnostics: the rows the tick kernels of tick t ran, summed over the shards held here

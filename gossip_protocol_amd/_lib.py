@@ -124,10 +124,21 @@ class GspCensusInfo(ctypes.Structure):
 _CENSUS = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(ctypes.c_uint32), P(ctypes.c_uint32),
                           P(ctypes.c_uint32), P(ctypes.c_uint8), P(GspCensusInfo)])
 
+class GspReachInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("direction", c_int32),
+                ("alive", c_int32), ("sources", c_int32), ("reached", c_int32), ("depth", c_int32),
+                ("levels", c_int32), ("sum_hops", c_int64), ("kernel_ms", ctypes.c_double)]
+
+
+_REACH = (ctypes.c_int, [ctypes.c_void_p, c_int32, c_int32, P(c_int32), c_int32, P(c_int32),
+                         P(ctypes.c_uint8), P(GspReachInfo)])
+
 # name -> (restype, argtypes); every name here must be exported (tests check it)
 SIGNATURES = {
     "gsp_scale_census": _CENSUS,
     "gsp_pview_census": _CENSUS,
+    "gsp_scale_reach": _REACH,
+    "gsp_pview_reach": _REACH,
     "gsp_last_error": (ctypes.c_char_p, []),
     "gsp_abi_version": (ctypes.c_int, []),
     "gsp_device_count": (ctypes.c_int, []),

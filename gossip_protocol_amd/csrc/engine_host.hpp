@@ -6,7 +6,7 @@
 // only those members.  Here: the stream, the timing-event pool, the failure / join schedule,
 // the communicator, the capacity flag and its host mirror, the single-shard CSR build, the
 // JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census
-// and the C-ABI bodies that are the same code.  Tables, tick arguments, kernels launched and
+// and of the overlay reach, and the C-ABI bodies that are the same code.  Tables, tick arguments, kernels launched and
 // test knobs stay with each engine.
 #pragma once
 #include <rccl/rccl.h>
@@ -20,6 +20,7 @@
 #include "event_ring.hpp"
 #include "join_kernels.hpp"
 #include "policy.hpp"
+#include "reach_kernels.hpp"
 #include "rowx_host.hpp"
 #include "scale_kernels.hpp"
 
@@ -63,6 +64,30 @@ struct CensusBufs {
     }
 };
 
+// The overlay-reach state (gsp_scale_reach / gsp_pview_reach), allocated by the first call and
+// shared by every local shard: hops[n], the two n-bit maps reach_level rewrites per level, the
+// cumulative count of reached nodes with its pinned mirror, and the sources' device copy.
+struct ReachBufs {
+    DevBuf<uint32_t> hops, count;
+    DevBuf<uint64_t> front, todo;
+    DevBuf<int32_t> src;
+    uint32_t *h_count = nullptr;   // pinned
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+
+    void release() {
+        hops.release();
+        count.release();
+        front.release();
+        todo.release();
+        src.release();
+        if (h_count) (void)hipHostFree(h_count);
+        h_count = nullptr;
+        for (hipEvent_t e : {t0, t1})
+            if (e) (void)hipEventDestroy(e);
+        t0 = t1 = nullptr;
+    }
+};
+
 struct EngineCore {
     int device = 0;
     hipStream_t st = nullptr;
@@ -85,6 +110,7 @@ struct EngineCore {
     std::vector<hipEvent_t> free_events;
     gsp_scale_perf perf{};
     CensusBufs census;
+    ReachBufs reach;
 
     void recycle(const Timed &t) {     // a tick's three events back to the pool
         for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
@@ -162,6 +188,7 @@ inline void engine_close(EngineCore &c) {
     for (hipEvent_t e : c.free_events) (void)hipEventDestroy(e);
     if (c.comm) (void)ncclCommDestroy(c.comm);
     c.census.release();
+    c.reach.release();
     c.rowx.release();
     if (c.h_err) (void)hipHostFree(c.h_err);
     if (c.st) (void)hipStreamDestroy(c.st);
@@ -488,6 +515,99 @@ int census_run(E &s, bool packed, int32_t age_limit, uint32_t *listed,
         float ms = 0.f;
         if (s.timing) GSP_HIP(hipEventElapsedTime(&ms, c.t0, c.t1));
         *info = gsp_census_info{T, s.p.n, age_limit, alive, entries, double(ms)};
+    }
+    return GSP_OK;
+}
+
+// The overlay reach of the engine's current tick T (gossip.h, reach_kernels.hpp), after the
+// engine has synchronised and reported any pending capacity error: a level-synchronous BFS, one
+// launch per local shard and level.  launch(shard, common, to) runs that shard's share of level
+// common.cur -- its rows, its columns -- on the engine's stream; with a communicator hops is
+// then all-reduced (MIN), so every rank must make the call at the same tick with the same
+// arguments.  After each level reach_level counts the nodes just reached into a device word the
+// host waits for: one host wait per level, and the loop ends at the first level that reaches
+// nobody.  The count word is cumulative, so it is zeroed once per call.
+template <class E, class Launch>
+int reach_run(E &s, const char *fn, int32_t direction, int32_t age_limit, const int32_t *sources,
+              int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info, Launch launch) {
+    GSP_REQUIRE(direction == GSP_REACH_FROM || direction == GSP_REACH_TO, GSP_ERR_INVALID,
+                "%s: direction=%d is neither GSP_REACH_FROM (0) nor GSP_REACH_TO (1)", fn, direction);
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID, "%s: age_limit=%d outside [1,32]",
+                fn, age_limit);
+    GSP_REQUIRE(sources && n_sources > 0, GSP_ERR_INVALID, "%s: no sources (n_sources=%d)", fn, n_sources);
+    for (int32_t i = 0; i < n_sources; ++i)
+        GSP_REQUIRE(sources[i] >= 0 && sources[i] < s.p.n, GSP_ERR_INVALID,
+                    "%s: sources[%d]=%d outside [0,%d)", fn, i, sources[i], s.p.n);
+    const size_t n = size_t(s.p.n), words = reach_bitmap_words(s.p.n);
+    const int32_t T = s.tick;
+    ReachBufs &b = s.reach;
+    if (!b.t1) {                       // first call (t1 is made last: a failed attempt starts over)
+        GSP_HIP(b.hops.alloc(n));
+        GSP_HIP(b.count.alloc(1));
+        GSP_HIP(b.front.alloc(words));
+        GSP_HIP(b.todo.alloc(words));
+        if (!b.h_count) GSP_HIP(hipHostMalloc(reinterpret_cast<void **>(&b.h_count), 4));
+        if (!b.t0) GSP_HIP(hipEventCreate(&b.t0));
+        GSP_HIP(hipEventCreate(&b.t1));
+    }
+    GSP_HIP(b.src.alloc(size_t(n_sources)));
+
+    ReachCommon c{};
+    c.n = s.p.n;
+    c.tick = T;
+    c.age_limit = age_limit;
+    c.fail_tick = s.local[0].fail_tick.p;
+    c.start_tick = s.joins ? s.local[0].start_tick.p : nullptr;
+    c.hops = b.hops.p;
+    c.front = b.front.p;
+    c.todo = b.todo.p;
+
+    // the nodes at `level`, from the cumulative count (waits for the stream)
+    uint32_t reached = 0;
+    auto count_level = [&](uint32_t level, uint32_t *found) -> int {
+        GSP_HIP(launch_reach_level(c, level, b.front.p, b.todo.p, b.count.p, s.st));
+        GSP_HIP(hipMemcpyAsync(b.h_count, b.count.p, 4, hipMemcpyDeviceToHost, s.st));
+        GSP_HIP(hipStreamSynchronize(s.st));
+        *found = *b.h_count - reached;
+        reached = *b.h_count;
+        return GSP_OK;
+    };
+
+    if (s.timing) GSP_HIP(hipEventRecord(b.t0, s.st));
+    GSP_HIP(hipMemcpyAsync(b.src.p, sources, size_t(n_sources) * 4, hipMemcpyHostToDevice, s.st));
+    GSP_HIP(hipMemsetAsync(b.hops.p, 0xFF, n * 4, s.st));          // kReachUnset
+    GSP_HIP(hipMemsetAsync(b.count.p, 0, 4, s.st));
+    GSP_HIP(launch_reach_seed(b.src.p, n_sources, c, s.st));
+    uint32_t level0 = 0, found = 0;
+    if (int rc = count_level(0, &level0)) return rc;
+    int32_t depth = -1, levels = 0;
+    int64_t sum_hops = 0;
+    found = level0;
+    while (found) {
+        depth = int32_t(c.cur);
+        sum_hops += int64_t(found) * depth;
+        for (auto &sh : s.local)
+            if (int rc = launch(sh, c, direction == GSP_REACH_TO)) return rc;
+        if (s.comm) GSP_NCCL(ncclAllReduce(b.hops.p, b.hops.p, n, ncclUint32, ncclMin, s.comm, s.st));
+        ++levels;
+        if (int rc = count_level(c.cur + 1, &found)) return rc;
+        ++c.cur;
+    }
+    if (s.timing) GSP_HIP(hipEventRecord(b.t1, s.st));
+    // unset is 0xFFFFFFFF: -1 as the caller's int32
+    if (hops) GSP_HIP(hipMemcpyAsync(hops, b.hops.p, n * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    int32_t alive = 0;
+    for (size_t x = 0; x < n; ++x) {
+        const uint8_t st = T < s.h_start[x] ? 0 : T <= s.h_fail[x] ? 1 : 2;
+        alive += st == 1;
+        if (state) state[x] = st;
+    }
+    if (info) {
+        float ms = 0.f;
+        if (s.timing) GSP_HIP(hipEventElapsedTime(&ms, b.t0, b.t1));
+        *info = gsp_reach_info{T, s.p.n, age_limit, direction, alive, int32_t(level0), int32_t(reached),
+                               depth, levels, sum_hops, double(ms)};
     }
     return GSP_OK;
 }

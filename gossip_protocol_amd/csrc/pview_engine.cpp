@@ -618,6 +618,26 @@ int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t
     });
 }
 
+// Overlay reach of the current tick (engine_host.hpp reach_run): per level every local shard
+// runs its rows.
+int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
+                    int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_reach: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::reach_run(*s, "gsp_pview_reach", direction, age_limit, sources, n_sources, hops, state, info,
+                          [&](PvShard &sh, const gsp::ReachCommon &c, bool to) -> int {
+        gsp::ReachPviewArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.len = sh.len[s->tick & 1].p;
+        a.view = s->p.view;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_reach_pview(a, to, s->st));
+        return GSP_OK;
+    });
+}
+
 int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out) {
     GSP_REQUIRE(s && out, GSP_ERR_INVALID, "gsp_pview_perf_get: NULL");
     if (int rc = gsp_pview_sync(s)) return rc;

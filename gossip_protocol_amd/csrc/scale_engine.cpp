@@ -729,6 +729,26 @@ int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t
     });
 }
 
+// Overlay reach of the current tick (engine_host.hpp reach_run): per level every local shard
+// runs its rows x columns -- the fused table, a column tile from col0, a row shard from row0.
+int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const int32_t *sources,
+                    int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_reach: NULL");
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::reach_run(*s, "gsp_scale_reach", direction, age_limit, sources, n_sources, hops, state, info,
+                          [&](Shard &sh, const gsp::ReachCommon &c, bool to) -> int {
+        gsp::ReachScaleArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.stride = s->stride;
+        a.col0 = sh.col0;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_reach_scale(a, to, s->st));
+        return GSP_OK;
+    });
+}
+
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {
     GSP_REQUIRE(s && stream, GSP_ERR_INVALID, "gsp_scale_hip_stream: NULL");
     *stream = reinterpret_cast<void *>(s->st);

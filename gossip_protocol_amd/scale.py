@@ -160,6 +160,17 @@ class ScaleEngine:
             age_limit = census.default_age_limit(self.params)
         return census.run(lib().gsp_scale_census, self._h, self.n, age_limit, "gsp_scale_census")
 
+    def reach(self, sources=0, direction="from", age_limit=None):
+        """BFS hop counts over the membership graph of the current tick (reach.Reach), from
+        (direction "from") or towards ("to") `sources`, an id or a sequence of ids; an edge is
+        an entry younger than age_limit (1..32), default as for census().  Collective across
+        the ranks of a job."""
+        from . import census, reach
+        if age_limit is None:
+            age_limit = census.default_age_limit(self.params)
+        return reach.run(lib().gsp_scale_reach, self._h, self.n, sources, direction, age_limit,
+                         "gsp_scale_reach")
+
     def drain_events(self):
         """(records, lost) since the last drain (events=True); see _lib.split_events."""
         return _lib.drain_events(lib().gsp_scale_drain_events, self._h)

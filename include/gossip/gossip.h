@@ -489,6 +489,46 @@ int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t
                      uint32_t *max_hb, uint8_t *state, gsp_census_info *info);
 
 /* ------------------------------------------------------------------------------------
+ * Overlay reach: hop counts over the membership graph of the engine's current tick T (every
+ * tick submitted so far; valid at T = 0), by a level-synchronous BFS on the tables in HBM.
+ * Nothing is added to create or step.  Vertices are the nodes alive at T (the census's rule:
+ * start[r] <= T <= crash[r]).  r -> x is an edge iff r and x are both alive, r's list holds x
+ * and (T - ts) mod 32 < age_limit (1..32; 32: every stored entry).  Rows that are not alive
+ * are never read, and entries for crashed members are not edges.
+ *   direction   GSP_REACH_FROM: hops[x] = fewest edges from any source to x (how soon what the
+ *               sources know can reach x); GSP_REACH_TO: hops[r] = fewest edges from r to any
+ *               source (whose gossip can reach the sources)
+ *   sources     n_sources ids in [0, n), the level-0 set; duplicates allowed, a source that is
+ *               not alive at T is ignored.  With no alive source the call succeeds: every hop
+ *               is -1, reached = 0, depth = -1.
+ *   hops[x]     n elements: -1 for every node that is not alive or not reached
+ *   state[x]    n elements, as in the census: 0 not started yet, 1 alive at T, 2 crashed
+ * hops, state and info may each be NULL.  The result is the same for every layout and number
+ * of shards.  One launch per local shard and level plus one host wait per level; a level costs
+ * about its frontier, not the table.  With a communicator the call is COLLECTIVE: hops is
+ * all-reduced (MIN) after every level, so every rank must make the call at the same tick with
+ * the same arguments, and every rank gets the whole result.  A pending capacity error returns
+ * GSP_ERR_CAPACITY as the other reads do.  The state (4 B + 2 bits per node) is allocated by
+ * the first call and freed at destroy.
+ * ---------------------------------------------------------------------------------- */
+#define GSP_REACH_FROM 0
+#define GSP_REACH_TO   1
+typedef struct {
+    int32_t tick, n, age_limit, direction;
+    int32_t alive;      /* nodes alive at T                                       */
+    int32_t sources;    /* distinct alive sources (level 0)                       */
+    int32_t reached;    /* nodes with hops >= 0, sources included                 */
+    int32_t depth;      /* largest hops value; -1 with no alive source            */
+    int32_t levels;     /* level launches made (depth + 1: the last reaches none) */
+    int64_t sum_hops;   /* sum of hops over reached nodes                         */
+    double kernel_ms;   /* HIP events around the seeding and the whole level loop,
+                           host waits between levels included (0: timing off)     */
+} gsp_reach_info;
+
+int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const int32_t *sources,
+                    int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);
+
+/* ------------------------------------------------------------------------------------
  * Event stream (params.events != 0): the tick kernels append every join / remove (partial
  * view: and evict) of the selected kinds as one 64-bit record kind << 62 | t << 42 | r << 21
  * | x (kind 1 join, 2 remove, 3 evict; r = the node whose list changed, x = the member) --
@@ -575,6 +615,9 @@ int gsp_pview_drain_stats(gsp_pview *s, int32_t classes, int64_t *rows, int64_t 
 /* As gsp_scale_census ("Membership census" above), over the views. */
 int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
                      uint32_t *max_hb, uint8_t *state, gsp_census_info *info);
+/* As gsp_scale_reach ("Overlay reach" above): a view is its row's out-edge list. */
+int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
+                    int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);
 /* As gsp_scale_drain_events (join / remove / evict records). */
 int gsp_pview_drain_events(gsp_pview *s, uint64_t *buf, int64_t cap, int64_t *n, int64_t *lost);
 /* Test diagnostics: the rows the tick kernels of tick t ran, summed over the shards held here

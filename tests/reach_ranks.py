@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""One rank of an overlay-reach run across ranks (tests/test_reach_rccl.py launches it under
+torch.distributed.run, one fresh process per GPU, no GPU call before it starts).
+
+    python -m torch.distributed.run --nproc-per-node N tests/reach_ranks.py <case>
+
+cases:
+  columns_tiled   full view, n = 3000, 2 column tiles per rank
+  rows            full view, n = 3000, row shards
+  pview_rows      partial view, n = 4096, view 32, row shards
+
+Every rank steps the engine 13 ticks and runs the CPU oracle on the same inputs.  Reach is
+collective: per level each rank runs the rows and columns it holds and hops is all-reduced
+(MIN) over RCCL, so EVERY rank's result at ticks 0, 12 and 13, in both directions, must equal
+the numpy BFS over the oracle's rows (tests/reach_oracle.py).  torch.distributed (gloo) carries
+only the RCCL id and the verdicts.  Rank 0 prints one JSON line; exit status 0 means parity.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+RANDOM = 1
+TICKS, AT, LIMITS = 13, (0, 12, 13), (3, 32)
+FIELDS = ("tick", "n", "age_limit", "direction", "alive", "sources", "reached", "depth", "levels",
+          "sum_hops")
+
+
+def run(case):
+    import torch.distributed as dist
+    from gossip_protocol_amd.dist import broadcast_bytes
+    from gossip_protocol_amd.scale import ScaleEngine, nccl_unique_id
+    from tests import reach_oracle as ro
+    from tests.oracle_binding import PviewOracle, ScaleOracle
+    dist.init_process_group("gloo")
+    rank, world = dist.get_rank(), dist.get_world_size()
+    dev = int(os.environ.get("LOCAL_RANK", "0"))
+    uid = broadcast_bytes(nccl_unique_id() if rank == 0 else None)
+    pview = case == "pview_rows"
+    if pview:
+        from gossip_protocol_amd.pview import PviewEngine
+        n = 4096
+        kw = dict(view=32, fanout=3, inbox=7, tremove=9, fail_mode=RANDOM, fail_tick=2,
+                  fail_ppm=50000, seed=4128)
+        orc = PviewOracle(n, **kw)
+        eng = PviewEngine(n, max_ticks=TICKS, device=dev, rank=rank, world=world, nccl_id=uid, **kw)
+    else:
+        n = 3000
+        kw = dict(fanout=3, tremove=9, fail_mode=RANDOM, fail_tick=2, fail_ppm=20000, seed=3003)
+        orc = ScaleOracle(n, **kw)
+        eng = ScaleEngine(n, max_ticks=TICKS, device=dev, rank=rank, world=world, nccl_id=uid,
+                          tiles=2 if case == "columns_tiled" else 1,
+                          layout="columns" if case == "columns_tiled" else "rows", **kw)
+    sets = ro.source_sets(orc, n, n - 1)
+    bad = []
+    for t in range(0, TICKS + 1):
+        if t:
+            orc.step()
+            eng.step(1)
+        if t not in AT:
+            continue
+        state = ro.states(orc, n, t)
+        edges = ro.edges_at(orc, n, state, pview)
+        for lim in LIMITS:
+            for dname, d in (("from", ro.FROM), ("to", ro.TO)):
+                adj = ro.graph(n, t, edges, lim, d)
+                for name, src in sets.items():
+                    hops, info = ro.expected(n, t, state, adj, lim, d, src)
+                    got = eng.reach(src, dname, lim)
+                    if not np.array_equal(got.hops, hops):
+                        bad.append(("hops", t, lim, dname, name, int((got.hops != hops).sum())))
+                    if not np.array_equal(got.state, state):
+                        bad.append(("state", t, lim, dname, name))
+                    if any(got.info[f] != info[f] for f in FIELDS):
+                        bad.append(("info", t, lim, dname, name, got.info))
+    eng.close()
+    orc.close()
+    res = [None] * world
+    dist.all_gather_object(res, {"rank": rank, "bad": [str(b)[:300] for b in bad]})
+    if rank == 0:
+        print(json.dumps({"case": case, "world": world, "ranks": res}), flush=True)
+    dist.destroy_process_group()
+    return 0 if not any(r["bad"] for r in res) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(run(sys.argv[1]))

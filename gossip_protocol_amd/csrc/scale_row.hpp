@@ -78,8 +78,9 @@ __device__ inline PackedConsts packed_consts(uint32_t t5, uint32_t tr) {
     return c;
 }
 
-// Same function as merge_word_scalar (checked exhaustively over hb in {0..3, 31, 100, 1000,
-// 2046, 2047} x every ts5 x every t5 x tr in {1, 5, 20, 31}):
+// Same function as merge_word_scalar; tests/test_param_edges_gpu.py runs both forms against the
+// CPU oracle at the ends of the ranges (hb 2040..2047 and across 1023 -> 1024, tr 1, and tr 31
+// over two wraps of ts5; the workloads are tests/param_edges.py's):
 //   present e:  m = max(v & hbmask, e); e' = m + (m != e) * t5
 //   absent e:   e' = v if v present and (t5 + 32 - ts5(v)) mod 32 < tr, else 0
 __device__ inline uint32_t merge_word_packed(uint32_t e, uint32_t v, const PackedConsts &c) {

@@ -10,6 +10,7 @@
 // the send lists, the draws, drop window and buffer admission -- runs in the HIP kernels
 // of exact_kernels.hip.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <numeric>
@@ -364,6 +365,22 @@ int gsp_create(const gsp_params *p, int device, gsp_rng_mode rng, uint64_t seed,
                 "gsp_create: unknown rng mode %d", int(rng));
     GSP_REQUIRE(p->intro_list >= 0 && p->intro_list <= 16, GSP_ERR_INVALID,
                 "gsp_create: intro_list=%d outside [0, 16]", p->intro_list);
+    // the admitted box of gsp_params (gossip.h), checked before any HIP call
+    GSP_REQUIRE(p->tremove >= 1, GSP_ERR_INVALID, "gsp_create: tremove=%d < 1", p->tremove);
+    GSP_REQUIRE(p->id_filter_limit >= 0, GSP_ERR_INVALID, "gsp_create: id_filter_limit=%d < 0",
+                p->id_filter_limit);
+    // make_key gives the queue index 20 bits, and gsp_tick_process refuses longer queues
+    GSP_REQUIRE(p->en_buff_size >= 0 && p->en_buff_size < (1 << 20), GSP_ERR_INVALID,
+                "gsp_create: en_buff_size=%d outside [0, 2^20)", p->en_buff_size);
+    GSP_REQUIRE(p->max_msg_size >= 0, GSP_ERR_INVALID, "gsp_create: max_msg_size=%d < 0",
+                p->max_msg_size);
+    GSP_REQUIRE(std::isfinite(p->msg_drop_prob) && p->msg_drop_prob >= 0 && p->msg_drop_prob <= 1,
+                GSP_ERR_INVALID, "gsp_create: msg_drop_prob=%g outside [0, 1]", p->msg_drop_prob);
+    GSP_REQUIRE(std::isfinite(p->step_rate) && p->step_rate >= 0, GSP_ERR_INVALID,
+                "gsp_create: step_rate=%g negative or not finite", p->step_rate);
+    GSP_REQUIRE(p->total_running_time >= 1 && p->total_running_time <= kMaxTicks, GSP_ERR_INVALID,
+                "gsp_create: total_running_time=%d outside [1, %d]", p->total_running_time,
+                kMaxTicks);
     *out = nullptr;
     int ndev = 0;
     GSP_HIP(hipGetDeviceCount(&ndev));
@@ -387,6 +404,13 @@ int gsp_create(const gsp_params *p, int device, gsp_rng_mode rng, uint64_t seed,
     e->nlist.assign(n, 0);
     e->recv_ctr.assign(size_t(n + 1) * kMaxTicks, 0);
     e->sent_host.assign(size_t(n + 1) * kMaxTicks, 0);
+    // Two ids of one strcmp() address class (256 and 512, the first pair): a message that
+    // lingers in the buffer for one of them -- failed, or not started yet -- is taken ticks
+    // later by the other, after its sender has committed newer lists (EmulNet.cpp:151-161).
+    // Even a driver that runs each phase as one batch then needs the send-time lists.
+    for (int32_t id = 2; id <= n && !e->snapshots; ++id)
+        for (int32_t other = 1; other < id && !e->snapshots; ++other)
+            e->snapshots = addr_class(id) == addr_class(other);
     if (dbg_log_path) {
         e->logf = std::fopen(dbg_log_path, "w");
         GSP_REQUIRE(e->logf, GSP_ERR_IO, "gsp_create: cannot write %s", dbg_log_path);

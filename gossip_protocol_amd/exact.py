@@ -148,11 +148,16 @@ class Engine:
 
 
 def run_application(conf_path, seed, rng="glibc", out_dir=".", device=0, ticks=None,
-                    state_dump=True, intro_list=0):
+                    state_dump=True, intro_list=0, params=None):
     """Run one testcase the way the reference Application does; returns output paths.
-    intro_list: gsp_params.intro_list, the opt-in bounded introducer list (0 = reference)."""
+    intro_list: gsp_params.intro_list, the opt-in bounded introducer list (0 = reference).
+    params: {gsp_params field: value} overrides applied after the .conf is read."""
     p = params_from_conf(conf_path)
     p.intro_list = intro_list
+    for field, value in (params or {}).items():
+        if field not in dict(p._fields_):
+            raise KeyError("gsp_params has no field %r" % field)
+        setattr(p, field, value)
     n = p.max_nnb
     T = p.total_running_time if ticks is None else ticks
     os.makedirs(out_dir, exist_ok=True)

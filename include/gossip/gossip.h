@@ -69,6 +69,18 @@ int gsp_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out
  * Params -- /root/reference/Params.{h,cpp}.  gsp_params_from_conf parses the same
  * four-key .conf grammar as Params::setparams (Params.cpp:19-43) and fills the same
  * hard-coded values (STEP_RATE 0.25, MAX_MSG_SIZE 4000, Params.cpp:29-31).
+ *
+ * The box gsp_create admits (anything outside: GSP_ERR_INVALID naming the field, before any
+ * HIP call):
+ *   max_nnb             1 .. 1024
+ *   msg_drop_prob       0 .. 1, finite (the threshold is (int)(100 p), EmulNet.cpp:92)
+ *   step_rate           >= 0, finite (0: every node starts at tick 0)
+ *   max_msg_size        >= 0 (every send is 40 + 16 bytes: <= 56 rejects all, >= 57 none)
+ *   en_buff_size        0 .. 2^20 - 1 (a node's queue index has 20 bits in the list order key)
+ *   total_running_time  1 .. 3600 (MAX_TIME, EmulNet.h:11)
+ *   tremove             >= 1
+ *   id_filter_limit     >= 0 (> max_nnb: no payload entry is filtered)
+ *   intro_list          0 .. 16
  * ---------------------------------------------------------------------------------- */
 typedef struct {
     int32_t max_nnb;            /* MAX_NNB -> EN_GPSZ, the number of peers             */
@@ -217,7 +229,10 @@ typedef struct {
 } gsp_queued_msg;
 
 /* Keep each sender's send-time list while messages carry it and the sender commits a newer
- * one (off by default: a driver that runs each phase as one batch never needs it).  Needed
+ * one.  Off by default below max_nnb = 512: a driver that runs each phase as one batch does not
+ * need it while every id has an address class of its own.  On from gsp_create at max_nnb >= 512,
+ * where ids 256 and 512 (then 768, 1024) compare equal under strcmp() (EmulNet.cpp:154) and one
+ * of them takes, ticks later, the messages that lingered for the other.  Needed
  * once messages can be handled in separate batches (driver callbacks, gsp_recv_callback,
  * gsp_add_member), so mp1_facade.hpp turns it on when its EmulNet is constructed: every
  * message admitted from then on holds its list, whatever receive path the driver takes

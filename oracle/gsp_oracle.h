@@ -30,7 +30,8 @@ void gsp_glibc_stream(uint32_t seed, int32_t *out, int64_t n);
 
 /* ---- exact MP1 restatement (mp1_oracle.c) ---- */
 enum { GSP_RNG_GLIBC = 0, GSP_RNG_PHILOX = 1 };
-/* Returns 0 on success, <0 on error.  Any output path may be NULL. */
+/* Returns 0 on success, <0 on error (-1 conf unreadable, -2 MAX_NNB outside 1..1024 or ticks
+ * outside 1..3600, -3 parameters outside their range).  Any output path may be NULL. */
 int gsp_oracle_mp1_run(const char *conf_path, uint64_t seed, int rng_mode, int ticks,
                        const char *dbg_path, const char *msgcount_path, const char *state_path,
                        const char *stdout_path);
@@ -133,6 +134,17 @@ void gsp_oracle_mp1_set_queue_trace(const char *path);
 /* opt-in bounded introducer list of the exact engine (gsp_params.intro_list); 0 = reference */
 void gsp_oracle_mp1_set_intro_list(int b);
 int64_t gsp_oracle_mp1_merges(void);
+/* the values the reference hard-codes, as parameters of the NEXT gsp_oracle_mp1_run only (every
+ * run ends by restoring the reference's; NULL restores them at once) */
+typedef struct {
+    int32_t tremove;          /* >= 1; T_REMOVE 20 (MP1Node.h:21)                            */
+    int32_t id_filter_limit;  /* >= 0; payload filter id < limit, 10 (MP1Node.cpp:245)       */
+    int32_t en_buff_size;     /* >= 0; ENBUFFSIZE 30000 (EmulNet.h:12)                       */
+    int32_t max_msg_size;     /* >= 0; MAX_MSG_SIZE 4000 (Params.cpp:31): a send is rejected
+                                 when 40 + sizeof(en_msg) = 56 >= max_msg_size (EmulNet.cpp:92) */
+    double step_rate;         /* >= 0; STEP_RATE 0.25 (Params.cpp:30)                        */
+} gsp_oracle_mp1_params;
+void gsp_oracle_mp1_set_params(const gsp_oracle_mp1_params *p);
 
 uint64_t gsp_event_mix(int kind, int64_t t, int64_t r, int64_t x);
 uint64_t gsp_pv_event_mix(int kind, int64_t t, int64_t r, int64_t x);   /* partial view */

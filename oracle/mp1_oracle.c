@@ -16,10 +16,27 @@
 #include "gsp_oracle.h"
 #include "gsp_philox.h"
 
-#define T_REMOVE 20          /* MP1Node.h:21                      */
-#define EN_BUFF_CAP 30000    /* EmulNet.h:12                      */
-#define ID_FILTER_LIMIT 10   /* MP1Node.cpp:245: id >= 0 && id < 10 */
 #define MAX_TICKS 3600       /* EmulNet.h:11 MAX_TIME             */
+#define MAX_N 1024           /* the exact engine's bound; the reference's own arrays stop at
+                                MAX_NODES = 1000 (EmulNet.h:10), so for 1001..1024 this
+                                restatement is the only reference */
+#define MSG_BYTES 40         /* sizeof(MessageHdr), MP1Node.h:43-47: the size of every send */
+#define EN_MSG_BYTES 16      /* sizeof(en_msg), EmulNet.h:23-30   */
+
+/* Run parameters the reference hard-codes.  gsp_oracle_mp1_set_params replaces them for the
+ * next run only: every run ends by putting the reference's values back. */
+#define REF_PARAMS { 20,     /* T_REMOVE, MP1Node.h:21                        */ \
+                     10,     /* MP1Node.cpp:245: id >= 0 && id < 10           */ \
+                     30000,  /* ENBUFFSIZE, EmulNet.h:12                      */ \
+                     4000,   /* MAX_MSG_SIZE, Params.cpp:31                   */ \
+                     0.25 }  /* STEP_RATE, Params.cpp:30                      */
+static const gsp_oracle_mp1_params k_ref_params = REF_PARAMS;
+static gsp_oracle_mp1_params g_par = REF_PARAMS;
+void gsp_oracle_mp1_set_params(const gsp_oracle_mp1_params *p) { g_par = p ? *p : k_ref_params; }
+#define T_REMOVE (g_par.tremove)
+#define EN_BUFF_CAP (g_par.en_buff_size)
+#define ID_FILTER_LIMIT (g_par.id_filter_limit)
+#define START_TICK(i) ((int)(g_par.step_rate * (i)))   /* Application.cpp:130, 143, 153 */
 
 enum { M_JOINREQ = 0, M_JOINREP = 1, M_GOSSIP = 3 }; /* MP1Node.h:31-36 */
 
@@ -37,6 +54,8 @@ typedef struct {
     int inited, in_group, failed;
     long hb;
     entry_t *list; int nlist;       /* ordered member list (vector order)    */
+    int *pos; int npos;             /* pos[id]: index of id in list, or -1 (ids 0..npos-1):
+                                       what check_exist's scan finds, without the scan */
     msg_t *queue; int nqueue, cap;  /* mp1q, FIFO                             */
 } node_t;
 
@@ -116,7 +135,7 @@ static int addr_key(int id) {
     return key;
 }
 
-/* sends the last gsp_oracle_mp1_run rejected because the 30,000-message buffer was full
+/* sends the last gsp_oracle_mp1_run rejected because the EmulNet buffer (30,000 messages) was full
  * (EmulNet.cpp:92): lets the fixture tests show that a case reaches that path */
 static int64_t g_buffer_full_rejects;
 /* optional handling-order trace (gsp_oracle_mp1_set_queue_trace) */
@@ -141,7 +160,8 @@ static void en_send(sim_t *s, int src_node, int dst_id, int type, const entry_t 
     int r = draw_send(s);                                  /* EmulNet.cpp:89, always drawn */
     int thr = (int)(s->drop_prob * 100);                   /* EmulNet.cpp:91               */
     if (s->nbuf >= EN_BUFF_CAP) { g_buffer_full_rejects++; return; }   /* EmulNet.cpp:92 */
-    if (s->dropmsg && r % 100 < thr) return;
+    if (MSG_BYTES + EN_MSG_BYTES >= g_par.max_msg_size) return;        /* EmulNet.cpp:92 */
+    if (s->dropmsg && r % 100 < thr) return;                           /* EmulNet.cpp:92 */
     msg_t m = {src_node + 1, dst_id, type, NULL, 0, addr_key(dst_id), s->t};
     if (type == M_GOSSIP && npl) {
         m.payload = malloc(sizeof(entry_t) * npl);
@@ -170,16 +190,20 @@ static void en_recv(sim_t *s, int node) {
 
 /* ---------------- MP1Node ---------------- */
 static entry_t *find(node_t *nd, int id) {               /* check_exist, MP1Node.cpp:308-326 */
-    for (int i = 0; i < nd->nlist; ++i)
-        if (nd->list[i].id == id) return &nd->list[i];
-    return NULL;
+    if (id < 0 || id >= nd->npos || nd->pos[id] < 0) return NULL;
+    return &nd->list[nd->pos[id]];
+}
+
+static void append(node_t *nd, entry_t e) {              /* memberList.push_back */
+    nd->pos[e.id] = nd->nlist;
+    nd->list[nd->nlist++] = e;
 }
 
 static void add_from_header(sim_t *s, int node, int src_id) { /* MP1Node.cpp:265-280 */
     node_t *nd = &s->nodes[node];
     if (find(nd, src_id)) return;
     entry_t e = {src_id, 1, s->t};
-    nd->list[nd->nlist++] = e;
+    append(nd, e);
     log_member(s, node, src_id, "joined");
 }
 
@@ -188,7 +212,7 @@ static void add_from_entry(sim_t *s, int node, const entry_t *v) { /* MP1Node.cp
     if (v->id == node + 1) return;
     if (s->t - v->ts < T_REMOVE) {
         log_member(s, node, v->id, "joined");
-        nd->list[nd->nlist++] = *v;
+        append(nd, *v);
     }
 }
 
@@ -255,8 +279,10 @@ static void node_ops(sim_t *s, int node) {               /* nodeLoopOps, MP1Node
     for (int i = nd->nlist - 1; i >= 0; --i) {
         if (s->t - nd->list[i].ts >= T_REMOVE) {
             log_member(s, node, nd->list[i].id, "removed");
+            nd->pos[nd->list[i].id] = -1;
             memmove(&nd->list[i], &nd->list[i + 1], sizeof(entry_t) * (nd->nlist - i - 1));
             nd->nlist--;
+            for (int k = i; k < nd->nlist; ++k) nd->pos[nd->list[k].id] = k;
         }
     }
     for (int i = 0; i < nd->nlist; ++i)
@@ -266,6 +292,7 @@ static void node_ops(sim_t *s, int node) {               /* nodeLoopOps, MP1Node
 static void node_start(sim_t *s, int node) {             /* MP1Node.cpp:67-154 */
     node_t *nd = &s->nodes[node];
     nd->failed = 0; nd->inited = 1; nd->in_group = 0; nd->hb = 0; nd->nlist = 0;
+    for (int k = 0; k < nd->npos; ++k) nd->pos[k] = -1;
     if (node + 1 == 1) {                                   /* introducer id 1, MP1Node.cpp:382 */
         log_line(s, node, "Starting up group...");
         nd->in_group = 1;
@@ -364,14 +391,26 @@ int gsp_oracle_mp1_run(const char *conf_path, uint64_t seed, int rng_mode, int t
     g_buffer_full_rejects = 0;
     g_merges = 0;
     g_trace = g_trace_path[0] ? fopen(g_trace_path, "w") : NULL;
-    if (read_conf(&s, conf_path) != 0) return -1;
-    if (s.n <= 0 || s.n > 1000 || ticks <= 0 || ticks > MAX_TICKS) return -2;
+    const int bad_par = g_par.tremove < 1 || g_par.id_filter_limit < 0 || g_par.en_buff_size < 0 ||
+                        g_par.max_msg_size < 0 || !(g_par.step_rate >= 0);
+    int rc = bad_par ? -3 : read_conf(&s, conf_path) != 0 ? -1 : 0;
+    if (!rc && (s.n <= 0 || s.n > MAX_N || ticks <= 0 || ticks > MAX_TICKS)) rc = -2;
+    if (rc) {
+        g_par = k_ref_params;
+        return rc;
+    }
     s.rng_mode = rng_mode;
     s.seed = seed;
     gsp_glibc_srand(&s.glibc, (uint32_t)seed);  /* the second srand (Application.cpp:96) rules */
     s.nodes = calloc(s.n, sizeof(node_t));
-    for (int i = 0; i < s.n; ++i) s.nodes[i].list = calloc(s.n + 1, sizeof(entry_t));
-    s.buf = calloc(EN_BUFF_CAP, sizeof(msg_t));
+    for (int i = 0; i < s.n; ++i) {
+        node_t *nd = &s.nodes[i];
+        nd->list = calloc(s.n + 1, sizeof(entry_t));
+        nd->npos = s.n + 1;
+        nd->pos = malloc(sizeof(int) * (size_t)nd->npos);
+        for (int k = 0; k < nd->npos; ++k) nd->pos[k] = -1;
+    }
+    s.buf = calloc((size_t)EN_BUFF_CAP + 1, sizeof(msg_t));
     s.sent = calloc((size_t)(s.n + 1) * MAX_TICKS, sizeof(int));
     s.recv = calloc((size_t)(s.n + 1) * MAX_TICKS, sizeof(int));
     s.dbg = dbg_path ? fopen(dbg_path, "w") : NULL;
@@ -383,13 +422,13 @@ int gsp_oracle_mp1_run(const char *conf_path, uint64_t seed, int rng_mode, int t
 
     for (s.t = 0; s.t < ticks; ++s.t) {                    /* Application.cpp:99 */
         for (int i = 0; i < s.n; ++i)                      /* phase R, Application.cpp:125-135 */
-            if (s.t > (int)(0.25 * i) && !s.nodes[i].failed) en_recv(&s, i);
+            if (s.t > START_TICK(i) && !s.nodes[i].failed) en_recv(&s, i);
         for (int i = s.n - 1; i >= 0; --i) {               /* phase P, Application.cpp:138-163 */
-            if (s.t == (int)(0.25 * i)) {
+            if (s.t == START_TICK(i)) {
                 node_start(&s, i);
                 if (out) fprintf(out, "%d-th introduced node is assigned with the address: %d:0\n",
                                  i, i + 1);
-            } else if (s.t > (int)(0.25 * i) && !s.nodes[i].failed) {
+            } else if (s.t > START_TICK(i) && !s.nodes[i].failed) {
                 node_loop(&s, i);
                 if (i == 0 && s.t % 500 == 0) {
                     char line[32];
@@ -411,8 +450,10 @@ int gsp_oracle_mp1_run(const char *conf_path, uint64_t seed, int rng_mode, int t
     for (int i = 0; i < s.n; ++i) {
         for (int k = 0; k < s.nodes[i].nqueue; ++k) free(s.nodes[i].queue[k].payload);
         free(s.nodes[i].list);
+        free(s.nodes[i].pos);
         free(s.nodes[i].queue);
     }
     free(s.nodes); free(s.buf); free(s.sent); free(s.recv);
+    g_par = k_ref_params;
     return 0;
 }

@@ -85,20 +85,20 @@ def state_digest(state_bytes):
     return sha, sel
 
 
-def write_big_conf(name):
-    nnb, single, drop = BIG_CONFS[name]
-    d = os.path.join(BIG_OUT, "testcases")
+def write_big_conf(name, confs=BIG_CONFS, out=BIG_OUT):
+    nnb, single, drop, prob = (confs[name] + ("0.1",))[:4]
+    d = os.path.join(out, "testcases")
     os.makedirs(d, exist_ok=True)
     with open(os.path.join(d, name + ".conf"), "w") as f:
-        f.write("MAX_NNB: %d\nSINGLE_FAILURE: %d\nDROP_MSG: %d\nMSG_DROP_PROB: 0.1\n"
-                % (nnb, single, drop))
+        f.write("MAX_NNB: %d\nSINGLE_FAILURE: %d\nDROP_MSG: %d\nMSG_DROP_PROB: %s\n"
+                % (nnb, single, drop, prob))
 
 
-def run_big(conf, seed, mode):
-    dest = os.path.join(BIG_OUT, mode, conf, str(seed))
+def run_big(conf, seed, mode, out=BIG_OUT):
+    dest = os.path.join(out, mode, conf, str(seed))
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "testcases"))
-        shutil.copy(os.path.join(BIG_OUT, "testcases", conf + ".conf"), os.path.join(tmp, "testcases"))
+        shutil.copy(os.path.join(out, "testcases", conf + ".conf"), os.path.join(tmp, "testcases"))
         env = dict(os.environ, GSP_SEED=str(seed), GSP_RNG=mode,
                    GSP_STATE_DUMP=os.path.join(tmp, "state.txt"))
         out = subprocess.run([BIN, "testcases/%s.conf" % conf], cwd=tmp, env=env,
@@ -124,11 +124,49 @@ def main_big():
             print("wrote", d, flush=True)
 
 
+# The exact engine's size and drop-probability edges (--edge), kept in the ref_big form: N at
+# and just past the lane counts of its batch kernel's blocks (64, 128, 256, 512 -> 65, 129, 257,
+# 513 take the next block), N = 1 and 2, the reference's MAX_NODES = 1000 (ids 768 and 1000; 768
+# aliases 256 and 512 under strcmp(), EmulNet.cpp:154), and MSG_DROP_PROB at 0, 1 and at 0.29,
+# whose threshold (int)(0.29 * 100) is 28 (EmulNet.cpp:92).
+EDGE_OUT = os.path.join(ROOT, "tests", "golden", "ref_edge")
+EDGE_CONFS = {
+    # name: (MAX_NNB, SINGLE_FAILURE, DROP_MSG, MSG_DROP_PROB)
+    "n1_single": (1, 1, 0, "0.1"), "n2_multi": (2, 0, 0, "0.1"), "n64_multi": (64, 0, 1, "0.1"),
+    "n65_single": (65, 1, 1, "0.1"), "n128_multi": (128, 0, 0, "0.1"),
+    "n129_single": (129, 1, 0, "0.1"), "n256_multi": (256, 0, 1, "0.1"),
+    "n257_single": (257, 1, 0, "0.1"), "n513_multi": (513, 0, 0, "0.1"),
+    "n1000_multidrop": (1000, 0, 1, "0.1"), "n10_drop0": (10, 1, 1, "0.0"),
+    "n10_drop029": (10, 1, 1, "0.29"), "n10_drop100": (10, 0, 1, "1.0"),
+}
+EDGE_RUNS = [(c, 3, m) for c in EDGE_CONFS
+             for m in {"n513_multi": ["glibc"], "n1000_multidrop": ["philox"]}.get(c, MODES)]
+EDGE_FILE_LIMIT = 200 * 1024
+
+
+def main_edge():
+    for c in EDGE_CONFS:
+        write_big_conf(c, EDGE_CONFS, EDGE_OUT)
+    # the longest runs first, so they overlap the many short ones
+    runs = sorted(EDGE_RUNS, key=lambda r: -EDGE_CONFS[r[0]][0])
+    with ThreadPoolExecutor(max_workers=6) as ex:
+        for d in ex.map(lambda a: run_big(*a, out=EDGE_OUT), runs):
+            print("wrote", d, flush=True)
+            for name in os.listdir(d):
+                size = os.path.getsize(os.path.join(d, name))
+                if size > EDGE_FILE_LIMIT:
+                    sys.exit("%s/%s is %d bytes, over the %d-byte limit of an edge fixture: "
+                             "drop that run" % (d, name, size, EDGE_FILE_LIMIT))
+
+
 def main():
     if not os.path.exists(BIN):
         sys.exit("build the reference first: make -C oracle ref")
     if "--big" in sys.argv:
         main_big()
+        return
+    if "--edge" in sys.argv:
+        main_edge()
         return
     for conf in CONFS:
         for seed in SEEDS:

@@ -83,6 +83,13 @@ class PviewDigest(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Mp1Params(ctypes.Structure):
+    """gsp_oracle_mp1_params (oracle/gsp_oracle.h): what the reference hard-codes."""
+    _fields_ = [("tremove", ctypes.c_int32), ("id_filter_limit", ctypes.c_int32),
+                ("en_buff_size", ctypes.c_int32), ("max_msg_size", ctypes.c_int32),
+                ("step_rate", ctypes.c_double)]
+
+
 _oracle = None
 
 
@@ -100,6 +107,7 @@ def load_oracle():
         L.gsp_oracle_mp1_buffer_full_rejects.restype = ctypes.c_int64
         L.gsp_oracle_mp1_set_intro_list.argtypes = [ctypes.c_int]
         L.gsp_oracle_mp1_merges.restype = ctypes.c_int64
+        L.gsp_oracle_mp1_set_params.argtypes = [ctypes.POINTER(Mp1Params)]
         L.gsp_glibc_stream.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32),
                                        ctypes.c_int64]
         L.gsp_scale_oracle_create.argtypes = [ctypes.POINTER(ScaleCfg)]
@@ -158,6 +166,8 @@ def golden(mode, conf, seed, name):
 def conf_path(conf):
     if conf in BIG_CONFS:
         return os.path.join(GOLDEN_BIG, "testcases", conf + ".conf")
+    if conf in EDGE_CONFS:
+        return os.path.join(GOLDEN_EDGE, "testcases", conf + ".conf")
     return os.path.join(GOLDEN, "testcases", conf + ".conf")
 
 
@@ -201,18 +211,38 @@ def outputs_for_big(paths):
     return out
 
 
-def run_oracle_mp1(conf, seed, mode, out_dir, ticks=700, intro_list=0):
-    """intro_list: the exact engine's opt-in bounded introducer list (0 = the reference)."""
+# Fixtures at the exact engine's size and drop-probability edges (make_golden.py --edge), made by
+# the reference and kept in the ref_big form.
+GOLDEN_EDGE = os.path.join(ROOT, "tests", "golden", "ref_edge")
+EDGE_CONFS = ["n1_single", "n2_multi", "n64_multi", "n65_single", "n128_multi", "n129_single",
+              "n256_multi", "n257_single", "n513_multi", "n1000_multidrop", "n10_drop0",
+              "n10_drop029", "n10_drop100"]
+EDGE_RUNS = [(c, 3, m) for c in EDGE_CONFS
+             for m in {"n513_multi": ["glibc"], "n1000_multidrop": ["philox"]}.get(c, MODES)]
+
+
+def golden_edge(mode, conf, seed, name):
+    with gzip.open(os.path.join(GOLDEN_EDGE, mode, conf, str(seed), name + ".gz"), "rb") as f:
+        return f.read()
+
+
+def run_oracle_mp1(conf, seed, mode, out_dir, ticks=700, intro_list=0, tremove=20,
+                   id_filter_limit=10, en_buff_size=30000, max_msg_size=4000, step_rate=0.25):
+    """intro_list: the exact engine's opt-in bounded introducer list (0 = the reference).
+    tremove .. step_rate: what the reference hard-codes (gsp_oracle_mp1_params), for this run."""
     L = load_oracle()
     os.makedirs(out_dir, exist_ok=True)
     p = lambda x: os.path.join(out_dir, x).encode()
     L.gsp_oracle_mp1_set_intro_list(intro_list)
+    L.gsp_oracle_mp1_set_params(ctypes.byref(Mp1Params(tremove, id_filter_limit, en_buff_size,
+                                                       max_msg_size, step_rate)))
     try:
         rc = L.gsp_oracle_mp1_run(conf_path(conf).encode(), seed, MODES.index(mode), ticks,
                                   p("dbg.log"), p("msgcount.log"), p("state.txt"),
                                   p("stdout.txt"))
     finally:
         L.gsp_oracle_mp1_set_intro_list(0)
+        L.gsp_oracle_mp1_set_params(None)
     assert rc == 0, rc
     return {f: os.path.join(out_dir, f) for f in FILES}
 

@@ -151,6 +151,53 @@ def test_engine_params_out_of_range_status_and_message():
             assert create(ctypes.byref(p), 0, ctypes.byref(h)) not in (0, invalid, rng), last_ok
 
 
+EXACT_BOX = [("tremove", 0), ("tremove", -5), ("id_filter_limit", -1), ("en_buff_size", -1),
+             ("en_buff_size", 2**20), ("max_msg_size", -1), ("msg_drop_prob", -0.01),
+             ("msg_drop_prob", 1.01), ("msg_drop_prob", float("nan")),
+             ("msg_drop_prob", float("inf")), ("step_rate", -0.25), ("step_rate", float("nan")),
+             ("step_rate", float("inf")), ("total_running_time", 0),
+             ("total_running_time", 3601), ("max_nnb", 0), ("max_nnb", 1025), ("intro_list", 17)]
+
+
+@pytest.mark.parametrize("field,value", EXACT_BOX, ids=lambda x: str(x))
+def test_gsp_create_rejects_params_outside_the_box(field, value):
+    """gsp_create refuses what the exact engine cannot run -- GSP_ERR_INVALID and a message that
+    names the field -- before any HIP call, so the check holds with or without a GPU."""
+    L = _lib.lib()
+    p = _lib.GspParams()
+    assert L.gsp_params_default(ctypes.byref(p)) == 0
+    setattr(p, field, value)
+    h = ctypes.c_void_p()
+    assert L.gsp_create(ctypes.byref(p), 0, 0, 1, None, ctypes.byref(h)) == -1, (field, value)
+    msg = L.gsp_last_error().decode()
+    assert re.search(r"\b%s\b" % field, msg), msg
+    assert not h.value
+
+
+EXACT_BOX_ENDS = [dict(tremove=1), dict(id_filter_limit=0), dict(en_buff_size=0),
+                  dict(en_buff_size=2**20 - 1), dict(max_msg_size=0), dict(msg_drop_prob=0.0),
+                  dict(msg_drop_prob=1.0), dict(step_rate=0.0), dict(total_running_time=1),
+                  dict(total_running_time=3600), dict(max_nnb=1), dict(max_nnb=1024)]
+
+
+@pytest.mark.parametrize("ok", EXACT_BOX_ENDS, ids=lambda x: str(x))
+def test_gsp_create_admits_the_ends_of_the_box(ok):
+    """The ends of the admitted box get past validation: with a GPU the engine is created,
+    without one gsp_create fails at the device (not GSP_ERR_INVALID)."""
+    L = _lib.lib()
+    p = _lib.GspParams()
+    assert L.gsp_params_default(ctypes.byref(p)) == 0
+    for k, v in ok.items():
+        setattr(p, k, v)
+    h = ctypes.c_void_p()
+    rc = L.gsp_create(ctypes.byref(p), 0, 0, 1, None, ctypes.byref(h))
+    if L.gsp_device_count() > 0:
+        assert rc == 0, L.gsp_last_error()
+        assert L.gsp_destroy(h) == 0
+    else:
+        assert rc not in (0, -1), ok
+
+
 def test_struct_layouts_match_the_header():
     """Every public struct the ctypes stub mirrors has the C ABI's size."""
     L = _lib.lib()

@@ -122,3 +122,20 @@ def test_big_fixtures_reach_the_reference_quirks(tmp_path):
     # indirectly, so far fewer join lines than the N (N - 1) of a full view
     joins = golden_big("glibc", "n300_single", 3, "dbg.log").count(b"joined")
     assert joins < 300 * 299 // 4
+
+
+# ---- the exact engine's size and drop-probability edges (tests/golden/ref_edge) -------------
+from tests.oracle_binding import EDGE_RUNS, golden_edge  # noqa: E402
+
+
+@pytest.mark.parametrize("conf,seed,mode", EDGE_RUNS, ids=lambda x: str(x))
+def test_oracle_matches_reference_edge(tmp_path, conf, seed, mode):
+    """The C restatement reproduces the reference over all 700 ticks at N = 1, 2, at and just
+    past the lane counts 64 / 128 / 256 / 512 of the exact engine's blocks, at the reference's
+    MAX_NODES = 1000 (ids 768 and 1000) and at MSG_DROP_PROB 0, 0.29 and 1: dbg.log,
+    msgcount.log, stdout byte for byte and the end-of-tick state of every node at every tick
+    (per-tick SHA-256, full lines at selected ticks)."""
+    got = outputs_for_big(run_oracle_mp1(conf, seed, mode, str(tmp_path)))
+    for name in BIG_FILES:
+        assert got[name] == golden_edge(mode, conf, seed, name), "%s %s %s %s" % (
+            conf, seed, mode, name)

@@ -36,6 +36,8 @@
 // gossipable at t - 1), SWIM (the probe of t - 1 resolved before TREMOVE) and the JOINREP's
 // bounded introducer list (node 0's gossipable members at the Philox ranks).
 // Oracle: oracle/pview_oracle.c with inbox = 0 (the sequential fold over every message).
+// tests/test_view_sizes_gpu.py walks V through the branches here: view < 8 (hub rows, d_merge_runs),
+// Vp = V against Vp > V (padded runs, the chunk sizing), per = 1 / 2 own-view slots a lane (V = 192 / 193).
 #include <cstdint>
 
 #include "join_kernels.hpp"

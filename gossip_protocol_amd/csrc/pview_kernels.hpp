@@ -106,6 +106,8 @@ struct PviewTickArgs {
 // Class 4 (kDrainHub): the rest, 1024-lane rows in two HBM buffers per workgroup (and every
 // row of a view below 8 slots).  long_list: kDrainHead words -- the rows of each class at [c],
 // their messages at [8 + c] -- then the rows of each class.
+// tests/test_view_sizes_gpu.py checks the view < 8 branch (V = 3, 7 against 8, 9) and every class
+// at runs that end in padding (Vp > V), per class against the oracle's message counts.
 constexpr int kDrainClasses = 5;
 constexpr int kDrainHub = 4;
 constexpr int kDrainHead = 16;

@@ -133,8 +133,30 @@ class GspReachInfo(ctypes.Structure):
 _REACH = (ctypes.c_int, [ctypes.c_void_p, c_int32, c_int32, P(c_int32), c_int32, P(c_int32),
                          P(ctypes.c_uint8), P(GspReachInfo)])
 
+
+class GspRumorInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("rumor", c_int32), ("seed_tick", c_int32),
+                ("sources", c_int32), ("alive", c_int32), ("known", c_int32),
+                ("known_alive", c_int32), ("last_heard", c_int32), ("ticks_traced", c_int32),
+                ("kernel_ms", ctypes.c_double)]
+
+
+_RUMOR_OPEN = (ctypes.c_int, [ctypes.c_void_p, c_int32])
+_RUMOR_SEED = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(c_int32), c_int32])
+_RUMOR_GET = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(c_int32), P(ctypes.c_uint8), P(c_int32),
+                             c_int32, P(GspRumorInfo)])
+_RUMOR_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
+
 # name -> (restype, argtypes); every name here must be exported (tests check it)
 SIGNATURES = {
+    "gsp_scale_rumor_open": _RUMOR_OPEN,
+    "gsp_scale_rumor_seed": _RUMOR_SEED,
+    "gsp_scale_rumor_get": _RUMOR_GET,
+    "gsp_scale_rumor_close": _RUMOR_CLOSE,
+    "gsp_pview_rumor_open": _RUMOR_OPEN,
+    "gsp_pview_rumor_seed": _RUMOR_SEED,
+    "gsp_pview_rumor_get": _RUMOR_GET,
+    "gsp_pview_rumor_close": _RUMOR_CLOSE,
     "gsp_scale_census": _CENSUS,
     "gsp_pview_census": _CENSUS,
     "gsp_scale_reach": _REACH,

@@ -5,9 +5,9 @@
 // plus their own tables each); the function templates below take the engine type E and read
 // only those members.  Here: the stream, the timing-event pool, the failure / join schedule,
 // the communicator, the capacity flag and its host mirror, the single-shard CSR build, the
-// JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census
-// and of the overlay reach, and the C-ABI bodies that are the same code.  Tables, tick arguments, kernels launched and
-// test knobs stay with each engine.
+// JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census,
+// of the overlay reach and of the rumor trace, and the C-ABI bodies that are the same code.
+// Tables, tick arguments, kernels launched and test knobs stay with each engine.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -22,6 +22,7 @@
 #include "policy.hpp"
 #include "reach_kernels.hpp"
 #include "rowx_host.hpp"
+#include "rumor_kernels.hpp"
 #include "scale_kernels.hpp"
 
 namespace gsp {
@@ -88,6 +89,33 @@ struct ReachBufs {
     }
 };
 
+// The rumor trace (gsp_*_rumor_*, rumor_kernels.hpp), allocated by open and freed by close, shared
+// by every local shard.  `red` stages the all-reduced heard / known of a get across row-shard
+// ranks, so the device state itself is never summed twice.
+struct RumorBufs {
+    bool open = false;
+    int32_t rumors = 0, ticks_traced = 0;
+    double kernel_ms = 0.0;
+    DevBuf<uint32_t> know, known, red;
+    DevBuf<int32_t> heard, src;
+    std::vector<int32_t> seed_tick;              // per rumor: first seed with an alive source
+    std::vector<std::vector<int32_t>> seeded;    // per rumor: the alive sources seeded, ascending
+    std::vector<int32_t> h_heard;
+    std::vector<uint32_t> h_known;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // timed ticks not yet collected
+
+    void release() {
+        for (auto *b : {&know, &known, &red}) b->release();
+        heard.release();
+        src.release();
+        seed_tick.clear();
+        seeded.clear();
+        open = false;
+        rumors = ticks_traced = 0;
+        kernel_ms = 0.0;
+    }
+};
+
 struct EngineCore {
     int device = 0;
     hipStream_t st = nullptr;
@@ -111,6 +139,7 @@ struct EngineCore {
     gsp_scale_perf perf{};
     CensusBufs census;
     ReachBufs reach;
+    RumorBufs rumor;
 
     void recycle(const Timed &t) {     // a tick's three events back to the pool
         for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
@@ -189,6 +218,9 @@ inline void engine_close(EngineCore &c) {
     if (c.comm) (void)ncclCommDestroy(c.comm);
     c.census.release();
     c.reach.release();
+    for (auto &e : c.rumor.pending) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+    c.rumor.pending.clear();
+    c.rumor.release();
     c.rowx.release();
     if (c.h_err) (void)hipHostFree(c.h_err);
     if (c.st) (void)hipStreamDestroy(c.st);
@@ -390,6 +422,15 @@ inline int collect_timing(EngineCore &c) {
         c.recycle(t);
     }
     c.pending.clear();
+    for (auto &e : c.rumor.pending) {          // the trace launches of the timed ticks
+        float ms = 0.f;
+        GSP_HIP(hipEventSynchronize(e.second));
+        GSP_HIP(hipEventElapsedTime(&ms, e.first, e.second));
+        c.rumor.kernel_ms += ms;
+        c.free_events.push_back(e.first);
+        c.free_events.push_back(e.second);
+    }
+    c.rumor.pending.clear();
     if (c.rowmode)
         if (int rc = rowx_collect(c.rowx, &c.perf.xgmi_bytes)) return rc;
     return GSP_OK;
@@ -609,6 +650,189 @@ int reach_run(E &s, const char *fn, int32_t direction, int32_t age_limit, const 
         *info = gsp_reach_info{T, s.p.n, age_limit, direction, alive, int32_t(level0), int32_t(reached),
                                depth, levels, sum_hops, double(ms)};
     }
+    return GSP_OK;
+}
+
+// ---- the rumor trace (gossip.h "Rumor trace", rumor_kernels.hpp) ----
+// Who computes what: without row shards (fused, column tiles, column shards across ranks) every
+// engine holds the job's whole receiver CSR in local[0] and runs all n rows from it, so ranks
+// need no exchange.  Row shards write their own rows of the shared know; across ranks know_cur is
+// zeroed, the held rows are written and the n words are all-reduced (MAX is exact: only the
+// holder writes a word, and a mask only gains bits, so a superset is never the smaller number),
+// while heard / known stay per rank until a get all-reduces them (MIN over an unset 0xFFFFFFFF,
+// SUM) into a staging buffer.
+
+template <class E>
+int rumor_open(E &s, const char *fn, int32_t rumors) {
+    RumorBufs &b = s.rumor;
+    GSP_REQUIRE(!b.open, GSP_ERR_INVALID, "%s: a trace is already open (%d rumors)", fn, b.rumors);
+    GSP_REQUIRE(rumors >= 1 && rumors <= kRumorMax, GSP_ERR_INVALID, "%s: rumors=%d outside [1,%d]", fn,
+                rumors, kRumorMax);
+    const size_t n = size_t(s.p.n), span = size_t(s.p.max_ticks) + 1;
+    GSP_HIP(b.know.alloc(2 * n));
+    GSP_HIP(b.heard.alloc(size_t(rumors) * n));
+    GSP_HIP(b.known.alloc(size_t(rumors) * span));
+    if (s.rowmode && s.comm) GSP_HIP(b.red.alloc(n + span));
+    GSP_HIP(hipMemsetAsync(b.know.p, 0, 2 * n * 4, s.st));
+    GSP_HIP(hipMemsetAsync(b.heard.p, 0xFF, size_t(rumors) * n * 4, s.st));     // -1: not heard
+    GSP_HIP(hipMemsetAsync(b.known.p, 0, size_t(rumors) * span * 4, s.st));
+    b.seed_tick.assign(size_t(rumors), -1);
+    b.seeded.assign(size_t(rumors), {});
+    b.rumors = rumors;
+    b.ticks_traced = 0;
+    b.kernel_ms = 0.0;
+    b.open = true;
+    return GSP_OK;
+}
+
+template <class E>
+int rumor_close(E &s, const char *fn) {
+    RumorBufs &b = s.rumor;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no trace is open", fn);
+    GSP_HIP(hipStreamSynchronize(s.st));           // no queued launch still uses the buffers
+    for (auto &e : b.pending) {
+        s.free_events.push_back(e.first);
+        s.free_events.push_back(e.second);
+    }
+    b.pending.clear();
+    b.release();
+    return GSP_OK;
+}
+
+// The seed rule at the engine's tick T, stream-ordered.  The host keeps the distinct alive
+// sources per rumor from its own copy of the schedule.
+template <class E>
+int rumor_seed(E &s, const char *fn, int32_t rumor, const int32_t *sources, int32_t n_sources) {
+    RumorBufs &b = s.rumor;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no trace is open", fn);
+    GSP_REQUIRE(rumor >= 0 && rumor < b.rumors, GSP_ERR_INVALID, "%s: rumor=%d outside [0,%d)", fn, rumor,
+                b.rumors);
+    GSP_REQUIRE(sources && n_sources > 0, GSP_ERR_INVALID, "%s: no sources (n_sources=%d)", fn, n_sources);
+    for (int32_t i = 0; i < n_sources; ++i)
+        GSP_REQUIRE(sources[i] >= 0 && sources[i] < s.p.n, GSP_ERR_INVALID,
+                    "%s: sources[%d]=%d outside [0,%d)", fn, i, sources[i], s.p.n);
+    const size_t n = size_t(s.p.n);
+    const int32_t T = s.tick;
+    GSP_HIP(b.src.alloc(size_t(n_sources)));
+    GSP_HIP(hipMemcpyAsync(b.src.p, sources, size_t(n_sources) * 4, hipMemcpyHostToDevice, s.st));
+    RumorSeedArgs a{};
+    a.n = s.p.n;
+    a.tick = T;
+    a.rumor = rumor;
+    a.lo = 0;
+    a.hi = s.p.n;
+    if (s.rowmode && s.comm) {                     // this rank records its own rows only
+        a.lo = s.local.front().row0;
+        a.hi = s.local.back().row0 + s.local.back().rows;
+    }
+    a.sources = b.src.p;
+    a.n_sources = n_sources;
+    a.fail_tick = s.local[0].fail_tick.p;
+    a.start_tick = s.joins ? s.local[0].start_tick.p : nullptr;
+    a.know = b.know.p + size_t(T & 1) * n;
+    a.heard = b.heard.p + size_t(rumor) * n;
+    a.known = b.known.p + size_t(rumor) * (size_t(s.p.max_ticks) + 1) + size_t(T);
+    GSP_HIP(launch_rumor_seed(a, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));           // seeding is between steps: the caller's array
+                                                   // and b.src are free again on return
+    std::vector<int32_t> &set = b.seeded[size_t(rumor)];
+    for (int32_t i = 0; i < n_sources; ++i) {
+        const size_t x = size_t(sources[i]);
+        if (s.h_start[x] <= T && T <= s.h_fail[x]) set.push_back(sources[i]);
+    }
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+    if (!set.empty() && b.seed_tick[size_t(rumor)] < 0) b.seed_tick[size_t(rumor)] = T;
+    return GSP_OK;
+}
+
+// Tick t of an open trace, on the engine's stream with no host wait: called where the receiver
+// CSR of t is complete and before the tick kernels.  fill(shard, args) adds what only the engine
+// knows (the partial view's receipt records).
+template <class E, class Fill>
+int rumor_step(E *s, int32_t t, Fill fill) {
+    RumorBufs &b = s->rumor;
+    const size_t n = size_t(s->p.n);
+    const uint32_t *prev = b.know.p + size_t((t + 1) & 1) * n;
+    uint32_t *cur = b.know.p + size_t(t & 1) * n;
+    const bool reduce = s->rowmode && s->comm;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (s->timing) {
+        e0 = s->event();
+        e1 = s->event();
+        GSP_HIP(hipEventRecord(e0, s->st));
+    }
+    if (reduce) GSP_HIP(hipMemsetAsync(cur, 0, n * 4, s->st));
+    for (auto &sh : s->local) {
+        if (!s->rowmode && &sh != &s->local[0]) continue;   // one CSR of all n rows
+        RumorTickArgs a{};
+        a.n = s->p.n;
+        a.tick = t;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        a.off = sh.off.p;
+        a.csr_src = sh.csr_src.p;
+        a.fail_tick = sh.fail_tick.p;
+        a.start_tick = s->joins ? sh.start_tick.p : nullptr;
+        a.know_prev = prev;
+        a.know_cur = cur;
+        a.heard = b.heard.p;
+        a.known = b.known.p;
+        a.known_stride = s->p.max_ticks + 1;
+        fill(sh, a);
+        GSP_HIP(launch_rumor_tick(a, s->st));
+    }
+    if (reduce) GSP_NCCL(ncclAllReduce(cur, cur, n, ncclUint32, ncclMax, s->comm, s->st));
+    if (s->timing) {
+        GSP_HIP(hipEventRecord(e1, s->st));
+        b.pending.emplace_back(e0, e1);
+    }
+    ++b.ticks_traced;
+    return GSP_OK;
+}
+
+// One rumor's result at the engine's tick T, after the engine has synchronised and reported any
+// pending capacity error.
+template <class E>
+int rumor_get(E &s, const char *fn, int32_t rumor, int32_t *heard, uint8_t *state, int32_t *known,
+              int32_t known_cap, gsp_rumor_info *info) {
+    RumorBufs &b = s.rumor;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no trace is open", fn);
+    GSP_REQUIRE(rumor >= 0 && rumor < b.rumors, GSP_ERR_INVALID, "%s: rumor=%d outside [0,%d)", fn, rumor,
+                b.rumors);
+    GSP_REQUIRE(known_cap >= 0 || !known, GSP_ERR_INVALID, "%s: known_cap=%d", fn, known_cap);
+    const size_t n = size_t(s.p.n), span = size_t(s.p.max_ticks) + 1;
+    const int32_t T = s.tick;
+    const int32_t *d_heard = b.heard.p + size_t(rumor) * n;
+    const uint32_t *d_known = b.known.p + size_t(rumor) * span;
+    if (s.rowmode && s.comm) {
+        GSP_NCCL(ncclAllReduce(d_heard, b.red.p, n, ncclUint32, ncclMin, s.comm, s.st));
+        GSP_NCCL(ncclAllReduce(d_known, b.red.p + n, span, ncclUint32, ncclSum, s.comm, s.st));
+        d_heard = reinterpret_cast<const int32_t *>(b.red.p);
+        d_known = b.red.p + n;
+    }
+    b.h_heard.resize(n);
+    b.h_known.resize(span);
+    GSP_HIP(hipMemcpyAsync(b.h_heard.data(), d_heard, n * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipMemcpyAsync(b.h_known.data(), d_known, span * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    int32_t alive = 0, cnt = 0, cnt_alive = 0, last = -1;
+    for (size_t x = 0; x < n; ++x) {
+        const uint8_t st = T < s.h_start[x] ? 0 : T <= s.h_fail[x] ? 1 : 2;
+        const int32_t h = b.h_heard[x];
+        alive += st == 1;
+        cnt += h >= 0;
+        cnt_alive += h >= 0 && st == 1;
+        last = std::max(last, h);
+        if (state) state[x] = st;
+    }
+    if (heard) std::memcpy(heard, b.h_heard.data(), n * 4);
+    if (known)
+        for (int32_t t = 0; t < known_cap && t <= T; ++t) known[t] = int32_t(b.h_known[size_t(t)]);
+    if (info)
+        *info = gsp_rumor_info{T, s.p.n, rumor, b.seed_tick[size_t(rumor)],
+                               int32_t(b.seeded[size_t(rumor)].size()), alive, cnt, cnt_alive, last,
+                               b.ticks_traced, s.timing ? b.kernel_ms : 0.0};
     return GSP_OK;
 }
 

@@ -471,6 +471,11 @@ int gsp_pview_step(gsp_pview *s, int32_t ticks) {
         // (hence its sync) names the same tick
         if (s->comm)
             GSP_NCCL(ncclAllReduce(s->local[0].err.p, s->local[0].err.p, 1, ncclInt32, ncclMax, s->comm, s->st));
+        if (s->rumor.open)       // bounded inbox: the receipt records name the senders merged
+            if (int rc = gsp::rumor_step(s, t, [&](PvShard &sh, gsp::RumorTickArgs &a) {
+                    a.rc_info = s->drain ? nullptr : sh.rc_info.p;
+                    a.rc_src = s->drain ? nullptr : sh.rc_src.p;
+                })) return rc;
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
         for (PvShard &sh : s->local) {
             gsp::PviewTickArgs ta = s->args(sh, t);
@@ -636,6 +641,33 @@ int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const in
         GSP_HIP(gsp::launch_reach_pview(a, to, s->st));
         return GSP_OK;
     });
+}
+
+// Rumor trace (engine_host.hpp rumor_*): a bounded inbox hears the senders of its receipt
+// record, drain all every entry of the segment.
+int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_open: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::rumor_open(*s, "gsp_pview_rumor_open", rumors);
+}
+
+int gsp_pview_rumor_seed(gsp_pview *s, int32_t rumor, const int32_t *sources, int32_t n_sources) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_seed: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::rumor_seed(*s, "gsp_pview_rumor_seed", rumor, sources, n_sources);
+}
+
+int gsp_pview_rumor_get(gsp_pview *s, int32_t rumor, int32_t *heard, uint8_t *state, int32_t *known,
+                        int32_t known_cap, gsp_rumor_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_get: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::rumor_get(*s, "gsp_pview_rumor_get", rumor, heard, state, known, known_cap, info);
+}
+
+int gsp_pview_rumor_close(gsp_pview *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_close: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::rumor_close(*s, "gsp_pview_rumor_close");
 }
 
 int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out) {

@@ -549,6 +549,8 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
             }
         }
         if (int rc = gsp::join_scatter(s, t, s->shared)) return rc;
+        if (s->rumor.open)       // the CSR of t is complete; the tick kernels may sort it in place
+            if (int rc = gsp::rumor_step(s, t, [](Shard &, gsp::RumorTickArgs &) {})) return rc;
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
         for (Shard &sh : s->local)
             GSP_HIP(gsp::launch_scale_tick(s->args(sh, t), s->sliced, s->merge, s->st));
@@ -747,6 +749,32 @@ int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const in
         GSP_HIP(gsp::launch_reach_scale(a, to, s->st));
         return GSP_OK;
     });
+}
+
+// Rumor trace (engine_host.hpp rumor_*): every entry of a receiver's segment is heard.
+int gsp_scale_rumor_open(gsp_scale *s, int32_t rumors) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_open: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::rumor_open(*s, "gsp_scale_rumor_open", rumors);
+}
+
+int gsp_scale_rumor_seed(gsp_scale *s, int32_t rumor, const int32_t *sources, int32_t n_sources) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_seed: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::rumor_seed(*s, "gsp_scale_rumor_seed", rumor, sources, n_sources);
+}
+
+int gsp_scale_rumor_get(gsp_scale *s, int32_t rumor, int32_t *heard, uint8_t *state, int32_t *known,
+                        int32_t known_cap, gsp_rumor_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_get: NULL");
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::rumor_get(*s, "gsp_scale_rumor_get", rumor, heard, state, known, known_cap, info);
+}
+
+int gsp_scale_rumor_close(gsp_scale *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_close: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::rumor_close(*s, "gsp_scale_rumor_close");
 }
 
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {

@@ -35,6 +35,18 @@ __device__ __forceinline__ uint64_t lane_of(uint64_t x, int32_t l) {      // two
     return (uint64_t(lane_of(uint32_t(x >> 32), l)) << 32) | lane_of(uint32_t(x), l);
 }
 
+// OR of x over the wave, in every lane: the scan's six DPP steps with | for + (a lane the shift
+// or the row mask leaves out takes 0), then lane 63's word
+__device__ __forceinline__ uint32_t wave_or32(uint32_t x) {
+    x |= dpp_take<0x111>(x);
+    x |= dpp_take<0x112>(x);
+    x |= dpp_take<0x114>(x);
+    x |= dpp_take<0x118>(x);
+    x |= dpp_take<0x142, 0xA>(x);
+    x |= dpp_take<0x143, 0xC>(x);
+    return lane_of(x, 63);
+}
+
 __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) { return lane_of(wave_incl_scan(v), 63); }
 
 // 64-bit wave sum (mod 2^64) from three 32-bit scans: the low word in two 16-bit halves (each

@@ -171,6 +171,28 @@ class ScaleEngine:
         return reach.run(lib().gsp_scale_reach, self._h, self.n, sources, direction, age_limit,
                          "gsp_scale_reach")
 
+    def rumor_open(self, rumors=32):
+        """Open a rumor trace of `rumors` (1..32) independent rumors (rumor.py): from now on
+        every tick also moves them one hop over the messages delivered.  Collective."""
+        from . import rumor
+        rumor.open_trace(lib().gsp_scale_rumor_open, self._h, rumors, "gsp_scale_rumor_open")
+
+    def rumor_seed(self, rumor, sources):
+        """Give rumor `rumor` to `sources` (an id or a sequence) at the current tick; sources
+        that are not alive are ignored.  Collective."""
+        from . import rumor as _r
+        _r.seed(lib().gsp_scale_rumor_seed, self._h, rumor, sources, "gsp_scale_rumor_seed")
+
+    def rumor(self, rumor=0):
+        """rumor.Rumor of one rumor at the current tick.  Collective."""
+        from . import rumor as _r
+        return _r.get(lib().gsp_scale_rumor_get, self._h, self.n, self.params.max_ticks, rumor,
+                      "gsp_scale_rumor_get")
+
+    def rumor_close(self):
+        """Free the trace; step is back to the launches it makes without one.  Collective."""
+        check(lib().gsp_scale_rumor_close(self._h), "gsp_scale_rumor_close")
+
     def drain_events(self):
         """(records, lost) since the last drain (events=True); see _lib.split_events."""
         return _lib.drain_events(lib().gsp_scale_drain_events, self._h)

@@ -544,6 +544,54 @@ int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const in
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);
 
 /* ------------------------------------------------------------------------------------
+ * Rumor trace: dissemination times over the messages the engine really delivers.  A trace
+ * carries up to 32 independent rumors, the bits of one 32-bit word per node; while one is open,
+ * every tick adds one small pull kernel per local shard over the tick's receiver CSR (JOINREPs
+ * included), ahead of the tick kernels.  With no trace open nothing is added to create or step.
+ *   know_t[x]   the rumors node x has heard by the end of tick t
+ *   heard[b][x] the tick at which bit b of know[x] was first set, -1 if never
+ * Alive at t is the census's rule, start[x] <= t <= crash[x].
+ *   seed    between steps, at the engine's tick T: every source alive at T gets bit `rumor`, and
+ *           heard = T where it was unset.  Duplicates and sources that are not alive are ignored;
+ *           a later seed of the same rumor adds sources.
+ *   tick t  a receiver r alive at t hears the OR of know_{t-1}[s] over the senders s whose
+ *           messages it merges at t -- every entry of its segment (full view; partial view with
+ *           inbox 0), or the `inbox` smallest senders of it (bounded partial view).  A JOINREP
+ *           rides like a GOSSIP from node 0, sorts first and takes an inbox slot.  know_t[r] =
+ *           know_{t-1}[r] | heard, and every bit newly set gives heard[b][r] = t.  A row that is
+ *           not alive at t keeps its mask.  Senders are read from know_{t-1} only: news moves one
+ *           hop per tick.  SWIM probes and TFAIL carry nothing.
+ * open     rumors in 1..32; an error while a trace is open.  Allocates know[2][n], heard[rumors][n]
+ *          and known[rumors][max_ticks + 1] on the device.
+ * get      synchronises (a pending capacity error returns GSP_ERR_CAPACITY as the other reads
+ *          do).  heard: n elements; state: n elements as in the census; known[t] for t <
+ *          min(known_cap, T + 1): the nodes whose heard[rumor] equals t, counted on the device.
+ *          Any pointer may be NULL.
+ * close    frees the trace; step is back to the launches it makes without one.
+ * The result is the same for every layout and number of shards.  With a communicator open,
+ * seed, get and close are COLLECTIVE (row shards all-reduce know each tick and heard / known at
+ * get), so every rank makes them at the same tick with the same arguments.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t tick, n, rumor;
+    int32_t seed_tick;    /* tick of the first seed with an alive source, -1: none yet     */
+    int32_t sources;      /* distinct sources that were alive when they were seeded        */
+    int32_t alive;        /* nodes alive at T                                              */
+    int32_t known;        /* nodes with heard >= 0                                         */
+    int32_t known_alive;  /* ... that are alive at T                                       */
+    int32_t last_heard;   /* largest heard value, -1 if nobody heard                       */
+    int32_t ticks_traced; /* ticks stepped since open                                      */
+    double kernel_ms;     /* HIP events around every tick's trace launches since open,
+                             collected at sync (0: timing off)                             */
+} gsp_rumor_info;
+
+int gsp_scale_rumor_open(gsp_scale *s, int32_t rumors);
+int gsp_scale_rumor_seed(gsp_scale *s, int32_t rumor, const int32_t *sources, int32_t n_sources);
+int gsp_scale_rumor_get(gsp_scale *s, int32_t rumor, int32_t *heard, uint8_t *state,
+                        int32_t *known, int32_t known_cap, gsp_rumor_info *info);
+int gsp_scale_rumor_close(gsp_scale *s);
+
+/* ------------------------------------------------------------------------------------
  * Event stream (params.events != 0): the tick kernels append every join / remove (partial
  * view: and evict) of the selected kinds as one 64-bit record kind << 62 | t << 42 | r << 21
  * | x (kind 1 join, 2 remove, 3 evict; r = the node whose list changed, x = the member) --
@@ -633,6 +681,12 @@ int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t
 /* As gsp_scale_reach ("Overlay reach" above): a view is its row's out-edge list. */
 int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);
+/* As gsp_scale_rumor_* ("Rumor trace" above); a bounded inbox hears its `inbox` smallest senders. */
+int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors);
+int gsp_pview_rumor_seed(gsp_pview *s, int32_t rumor, const int32_t *sources, int32_t n_sources);
+int gsp_pview_rumor_get(gsp_pview *s, int32_t rumor, int32_t *heard, uint8_t *state,
+                        int32_t *known, int32_t known_cap, gsp_rumor_info *info);
+int gsp_pview_rumor_close(gsp_pview *s);
 /* As gsp_scale_drain_events (join / remove / evict records). */
 int gsp_pview_drain_events(gsp_pview *s, uint64_t *buf, int64_t cap, int64_t *n, int64_t *lost);
 /* Test diagnostics: the rows the tick kernels of tick t ran, summed over the shards held here

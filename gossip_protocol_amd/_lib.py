@@ -147,8 +147,29 @@ _RUMOR_GET = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(c_int32), P(ctypes.c_ui
                              c_int32, P(GspRumorInfo)])
 _RUMOR_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
 
+
+
+class GspDetectInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("open_tick", c_int32), ("kinds", c_int32),
+                ("ticks_folded", c_int32), ("reserved", c_int32), ("records", c_int64),
+                ("lost", c_int64), ("true_removes", c_int64), ("false_removes", c_int64),
+                ("joins", c_int64), ("revivals", c_int64), ("evicts", c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
+_DETECT_OPEN = (ctypes.c_int, [ctypes.c_void_p])
+_DETECT_GET = (ctypes.c_int, [ctypes.c_void_p, P(c_int32), P(c_int32), P(ctypes.c_uint32),
+                              P(ctypes.c_uint32), P(c_int32), P(ctypes.c_uint32), P(ctypes.c_uint32),
+                              P(ctypes.c_uint8), P(c_uint64), c_int32, P(GspDetectInfo)])
+
 # name -> (restype, argtypes); every name here must be exported (tests check it)
 SIGNATURES = {
+    "gsp_scale_detect_open": _DETECT_OPEN,
+    "gsp_scale_detect_get": _DETECT_GET,
+    "gsp_scale_detect_close": _DETECT_OPEN,
+    "gsp_pview_detect_open": _DETECT_OPEN,
+    "gsp_pview_detect_get": _DETECT_GET,
+    "gsp_pview_detect_close": _DETECT_OPEN,
     "gsp_scale_rumor_open": _RUMOR_OPEN,
     "gsp_scale_rumor_seed": _RUMOR_SEED,
     "gsp_scale_rumor_get": _RUMOR_GET,

@@ -6,17 +6,20 @@
 // only those members.  Here: the stream, the timing-event pool, the failure / join schedule,
 // the communicator, the capacity flag and its host mirror, the single-shard CSR build, the
 // JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census,
-// of the overlay reach and of the rumor trace, and the C-ABI bodies that are the same code.
+// of the overlay reach, of the rumor trace and of the detection ledger, and the C-ABI bodies that
+// are the same code.
 // Tables, tick arguments, kernels launched and test knobs stay with each engine.
 #pragma once
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "census_kernels.hpp"
 #include "common.hpp"
+#include "detect_kernels.hpp"
 #include "event_ring.hpp"
 #include "join_kernels.hpp"
 #include "policy.hpp"
@@ -116,6 +119,32 @@ struct RumorBufs {
     }
 };
 
+// The detection ledger (gsp_*_detect_*, detect_kernels.hpp), allocated by open and freed by close,
+// shared by every local shard: every shard's ring folds into the one ledger (column tiles hold
+// disjoint x, row shards disjoint r).  `red` / `red64` stage the all-reduced arrays of a get
+// across ranks, so the device state itself is never summed twice.
+struct DetectBufs {
+    bool open = false;
+    int form = kDetectAggregated;                // GSP_TEST_DETECT_FORM=0|1 (tests, A/B) overrides
+    int32_t open_tick = 0, ticks_folded = 0;
+    double kernel_ms = 0.0;
+    DevBuf<int32_t> crash;                       // [n] h_fail
+    DevBuf<uint32_t> arr, red;                   // [kDetFields][n]
+    DevBuf<unsigned long long> wide, red64;      // by_tick[span][4], then tot[kDetTotals]
+    std::vector<uint32_t> h_arr;
+    std::vector<unsigned long long> h_wide;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // timed folds not yet collected
+
+    void release() {
+        crash.release();
+        for (auto *b : {&arr, &red}) b->release();
+        for (auto *b : {&wide, &red64}) b->release();
+        open = false;
+        open_tick = ticks_folded = 0;
+        kernel_ms = 0.0;
+    }
+};
+
 struct EngineCore {
     int device = 0;
     hipStream_t st = nullptr;
@@ -140,6 +169,7 @@ struct EngineCore {
     CensusBufs census;
     ReachBufs reach;
     RumorBufs rumor;
+    DetectBufs detect;
 
     void recycle(const Timed &t) {     // a tick's three events back to the pool
         for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
@@ -221,6 +251,9 @@ inline void engine_close(EngineCore &c) {
     for (auto &e : c.rumor.pending) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
     c.rumor.pending.clear();
     c.rumor.release();
+    for (auto &e : c.detect.pending) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+    c.detect.pending.clear();
+    c.detect.release();
     c.rowx.release();
     if (c.h_err) (void)hipHostFree(c.h_err);
     if (c.st) (void)hipStreamDestroy(c.st);
@@ -431,6 +464,15 @@ inline int collect_timing(EngineCore &c) {
         c.free_events.push_back(e.second);
     }
     c.rumor.pending.clear();
+    for (auto &e : c.detect.pending) {         // the folds of the timed ticks
+        float ms = 0.f;
+        GSP_HIP(hipEventSynchronize(e.second));
+        GSP_HIP(hipEventElapsedTime(&ms, e.first, e.second));
+        c.detect.kernel_ms += ms;
+        c.free_events.push_back(e.first);
+        c.free_events.push_back(e.second);
+    }
+    c.detect.pending.clear();
     if (c.rowmode)
         if (int rc = rowx_collect(c.rowx, &c.perf.xgmi_bytes)) return rc;
     return GSP_OK;
@@ -833,6 +875,154 @@ int rumor_get(E &s, const char *fn, int32_t rumor, int32_t *heard, uint8_t *stat
         *info = gsp_rumor_info{T, s.p.n, rumor, b.seed_tick[size_t(rumor)],
                                int32_t(b.seeded[size_t(rumor)].size()), alive, cnt, cnt_alive, last,
                                b.ticks_traced, s.timing ? b.kernel_ms : 0.0};
+    return GSP_OK;
+}
+
+// ---- the detection ledger (gossip.h "Detection ledger", detect_kernels.hpp) ----
+
+// One fold, stream-ordered with no host wait: every local shard's ring into the ledger, then the
+// shard's counters zeroed by a memset behind its launch.  Called where every writer of the tick
+// has been queued on the engine's stream.
+template <class E>
+int detect_fold(E *s) {
+    DetectBufs &b = s->detect;
+    const size_t span = size_t(s->p.max_ticks) + 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (s->timing) {
+        e0 = s->event();
+        e1 = s->event();
+        GSP_HIP(hipEventRecord(e0, s->st));
+    }
+    for (auto &sh : s->local) {
+        DetectFoldArgs a{};
+        a.ev = sh.ev.args();
+        a.n = s->p.n;
+        a.span = int32_t(span);
+        a.crash = b.crash.p;
+        a.arr = b.arr.p;
+        a.by_tick = b.wide.p;
+        a.tot = b.wide.p + span * 4;
+        GSP_HIP(launch_detect_fold(a, b.form, s->st));
+        GSP_HIP(hipMemsetAsync(sh.ev.count.p, 0, size_t(kEvStripes) * kEvCounterStride * 8, s->st));
+    }
+    if (s->timing) {
+        GSP_HIP(hipEventRecord(e1, s->st));
+        b.pending.emplace_back(e0, e1);
+    }
+    return GSP_OK;
+}
+
+template <class E>
+int detect_open(E &s, const char *fn) {
+    DetectBufs &b = s.detect;
+    GSP_REQUIRE(!b.open, GSP_ERR_INVALID, "%s: a ledger is already open (since tick %d)", fn, b.open_tick);
+    GSP_REQUIRE(s.p.events != 0 && (s.local[0].ev.kinds & GSP_EVENTS_REMOVE), GSP_ERR_INVALID,
+                "%s: the engine does not record removes (params.events = %d; needs GSP_EVENTS_ALL or "
+                "GSP_EVENTS_REMOVE)", fn, s.p.events);
+    const size_t n = size_t(s.p.n), span = size_t(s.p.max_ticks) + 1, wide = span * 4 + kDetTotals;
+    GSP_HIP(b.crash.alloc(n));
+    GSP_HIP(b.arr.alloc(size_t(kDetFields) * n));
+    GSP_HIP(b.wide.alloc(wide));
+    if (s.comm) {
+        GSP_HIP(b.red.alloc(size_t(kDetFields) * n));
+        GSP_HIP(b.red64.alloc(wide));
+    }
+    GSP_HIP(hipMemcpyAsync(b.crash.p, s.h_fail.data(), n * 4, hipMemcpyHostToDevice, s.st));
+    GSP_HIP(hipMemsetAsync(b.arr.p, 0, size_t(kDetFields) * n * 4, s.st));
+    for (int f : {int(kDetFirst), int(kDetFirstFalse)})                        // ~0: none
+        GSP_HIP(hipMemsetAsync(b.arr.p + size_t(f) * n, 0xFF, n * 4, s.st));
+    GSP_HIP(hipMemsetAsync(b.wide.p, 0, wide * 8, s.st));
+    b.form = kDetectAggregated;
+    if (const char *f = std::getenv("GSP_TEST_DETECT_FORM")) b.form = std::atoi(f) ? kDetectAggregated : kDetectPlain;
+    b.open_tick = s.tick;
+    b.ticks_folded = 0;
+    b.kernel_ms = 0.0;
+    b.open = true;
+    if (int rc = detect_fold(&s)) {            // what the ring holds now: every record since the last drain
+        b.open = false;
+        return rc;
+    }
+    GSP_HIP(hipStreamSynchronize(s.st));       // open is between steps: the schedule's copy is done on return
+    return GSP_OK;
+}
+
+template <class E>
+int detect_close(E &s, const char *fn) {
+    DetectBufs &b = s.detect;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no ledger is open", fn);
+    GSP_HIP(hipStreamSynchronize(s.st));           // no queued launch still uses the buffers
+    for (auto &e : b.pending) {
+        s.free_events.push_back(e.first);
+        s.free_events.push_back(e.second);
+    }
+    b.pending.clear();
+    b.release();
+    return GSP_OK;
+}
+
+// the fold of one stepped tick
+template <class E>
+int detect_step(E *s) {
+    if (int rc = detect_fold(s)) return rc;
+    ++s->detect.ticks_folded;
+    return GSP_OK;
+}
+
+// The ledger at the engine's tick T, after the engine has synchronised and reported any pending
+// capacity error.
+template <class E>
+int detect_get(E &s, const char *fn, int32_t *first_remove, int32_t *last_remove, uint32_t *removers,
+               uint32_t *false_removes, int32_t *first_false, uint32_t *revivals, uint32_t *evicts,
+               uint8_t *state, uint64_t *by_tick, int32_t by_tick_cap, gsp_detect_info *info) {
+    DetectBufs &b = s.detect;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no ledger is open", fn);
+    GSP_REQUIRE(by_tick_cap >= 0 || !by_tick, GSP_ERR_INVALID, "%s: by_tick_cap=%d", fn, by_tick_cap);
+    const size_t n = size_t(s.p.n), span = size_t(s.p.max_ticks) + 1, wide = span * 4 + kDetTotals;
+    const int32_t T = s.tick;
+    const uint32_t *d_arr = b.arr.p;
+    const unsigned long long *d_wide = b.wide.p;
+    if (s.comm) {
+        auto reduce = [&](int f, int fields, ncclRedOp_t op) {
+            return ncclAllReduce(b.arr.p + size_t(f) * n, b.red.p + size_t(f) * n, size_t(fields) * n,
+                                 ncclUint32, op, s.comm, s.st);
+        };
+        GSP_NCCL(reduce(kDetFirst, 1, ncclMin));
+        GSP_NCCL(reduce(kDetLast, 1, ncclMax));
+        GSP_NCCL(reduce(kDetRemovers, 2, ncclSum));        // removers, false_removes
+        GSP_NCCL(reduce(kDetFirstFalse, 1, ncclMin));
+        GSP_NCCL(reduce(kDetRevivals, 2, ncclSum));        // revivals, evicts
+        GSP_NCCL(ncclAllReduce(b.wide.p, b.red64.p, wide, ncclUint64, ncclSum, s.comm, s.st));
+        d_arr = b.red.p;
+        d_wide = b.red64.p;
+    }
+    b.h_arr.resize(size_t(kDetFields) * n);
+    b.h_wide.resize(wide);
+    GSP_HIP(hipMemcpyAsync(b.h_arr.data(), d_arr, b.h_arr.size() * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipMemcpyAsync(b.h_wide.data(), d_wide, wide * 8, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    const uint32_t *h = b.h_arr.data();
+    for (size_t x = 0; x < n; ++x) {
+        // first_*: ~0 is -1 as the caller's int32; last_remove holds t + 1
+        if (first_remove) first_remove[x] = int32_t(h[size_t(kDetFirst) * n + x]);
+        if (last_remove) last_remove[x] = int32_t(h[size_t(kDetLast) * n + x]) - 1;
+        if (removers) removers[x] = h[size_t(kDetRemovers) * n + x];
+        if (false_removes) false_removes[x] = h[size_t(kDetFalse) * n + x];
+        if (first_false) first_false[x] = int32_t(h[size_t(kDetFirstFalse) * n + x]);
+        if (revivals) revivals[x] = h[size_t(kDetRevivals) * n + x];
+        if (evicts) evicts[x] = h[size_t(kDetEvicts) * n + x];
+        if (state) state[x] = T < s.h_start[x] ? 0 : T <= s.h_fail[x] ? 1 : 2;
+    }
+    if (by_tick)
+        for (int32_t t = 0; t < by_tick_cap && t <= T; ++t)
+            for (int c = 0; c < 4; ++c) by_tick[size_t(t) * 4 + c] = b.h_wide[size_t(t) * 4 + c];
+    if (info) {
+        const unsigned long long *tot = b.h_wide.data() + span * 4;
+        *info = gsp_detect_info{T, s.p.n, b.open_tick, int32_t(s.local[0].ev.kinds), b.ticks_folded, 0,
+                                int64_t(tot[kDetRecords]), int64_t(tot[kDetLost]), int64_t(tot[kDetTrue]),
+                                int64_t(tot[kDetFalseTot]), int64_t(tot[kDetJoins]),
+                                int64_t(tot[kDetRevived]), int64_t(tot[kDetEvicted]),
+                                s.timing ? b.kernel_ms : 0.0};
+    }
     return GSP_OK;
 }
 

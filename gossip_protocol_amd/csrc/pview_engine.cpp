@@ -498,6 +498,8 @@ int gsp_pview_step(gsp_pview *s, int32_t ticks) {
             GSP_HIP(hipEventRecord(tm.c, s->st));
             s->pending.push_back(tm);
         }
+        if (s->detect.open)      // the hub kernel's stream has joined back: fold, empty the ring
+            if (int rc = gsp::detect_step(s)) return rc;
         if (int rc = gsp::join_sends(s, t, join_form(s))) return rc;
         s->tick = t;
         s->perf.ticks++;
@@ -668,6 +670,29 @@ int gsp_pview_rumor_close(gsp_pview *s) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_close: NULL");
     GSP_HIP(hipSetDevice(s->device));
     return gsp::rumor_close(*s, "gsp_pview_rumor_close");
+}
+
+// Detection ledger (engine_host.hpp detect_*): join, remove and evict records.
+int gsp_pview_detect_open(gsp_pview *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_detect_open: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::detect_open(*s, "gsp_pview_detect_open");
+}
+
+int gsp_pview_detect_get(gsp_pview *s, int32_t *first_remove, int32_t *last_remove, uint32_t *removers,
+                         uint32_t *false_removes, int32_t *first_false, uint32_t *revivals,
+                         uint32_t *evicts, uint8_t *state, uint64_t *by_tick, int32_t by_tick_cap,
+                         gsp_detect_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_detect_get: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::detect_get(*s, "gsp_pview_detect_get", first_remove, last_remove, removers, false_removes,
+                           first_false, revivals, evicts, state, by_tick, by_tick_cap, info);
+}
+
+int gsp_pview_detect_close(gsp_pview *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_detect_close: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::detect_close(*s, "gsp_pview_detect_close");
 }
 
 int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out) {

@@ -566,6 +566,8 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
             GSP_HIP(hipEventRecord(tm.c, s->st));
             s->pending.push_back(tm);
         }
+        if (s->detect.open)      // every writer of the tick's records is queued: fold, empty the ring
+            if (int rc = gsp::detect_step(s)) return rc;
         if (s->sliced)
             if (int rc = resolve_sends(s, t)) return rc;
         if (s->rowmode)
@@ -775,6 +777,29 @@ int gsp_scale_rumor_close(gsp_scale *s) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_close: NULL");
     GSP_HIP(hipSetDevice(s->device));
     return gsp::rumor_close(*s, "gsp_scale_rumor_close");
+}
+
+// Detection ledger (engine_host.hpp detect_*): every local shard's ring folds into one ledger.
+int gsp_scale_detect_open(gsp_scale *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_detect_open: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::detect_open(*s, "gsp_scale_detect_open");
+}
+
+int gsp_scale_detect_get(gsp_scale *s, int32_t *first_remove, int32_t *last_remove, uint32_t *removers,
+                         uint32_t *false_removes, int32_t *first_false, uint32_t *revivals,
+                         uint32_t *evicts, uint8_t *state, uint64_t *by_tick, int32_t by_tick_cap,
+                         gsp_detect_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_detect_get: NULL");
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::detect_get(*s, "gsp_scale_detect_get", first_remove, last_remove, removers, false_removes,
+                           first_false, revivals, evicts, state, by_tick, by_tick_cap, info);
+}
+
+int gsp_scale_detect_close(gsp_scale *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_detect_close: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::detect_close(*s, "gsp_scale_detect_close");
 }
 
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {

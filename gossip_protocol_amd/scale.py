@@ -193,6 +193,21 @@ class ScaleEngine:
         """Free the trace; step is back to the launches it makes without one.  Collective."""
         check(lib().gsp_scale_rumor_close(self._h), "gsp_scale_rumor_close")
 
+    def detect_open(self):
+        """Open the detection ledger (detect.py; needs events with removes recorded): what the
+        ring holds is folded now, and from now on every tick ends with one fold of its event
+        records per member on the device, which empties the ring."""
+        check(lib().gsp_scale_detect_open(self._h), "gsp_scale_detect_open")
+
+    def detect(self):
+        """detect.Detect of the open ledger at the current tick.  Collective."""
+        from . import detect
+        return detect.get(lib().gsp_scale_detect_get, self._h, self.params, "gsp_scale_detect_get")
+
+    def detect_close(self):
+        """Free the ledger; the ring is left empty and fills and drains as before.  Collective."""
+        check(lib().gsp_scale_detect_close(self._h), "gsp_scale_detect_close")
+
     def drain_events(self):
         """(records, lost) since the last drain (events=True); see _lib.split_events."""
         return _lib.drain_events(lib().gsp_scale_drain_events, self._h)

@@ -612,6 +612,56 @@ int gsp_scale_drain_events(gsp_scale *s, uint64_t *buf, int64_t cap, int64_t *n,
 int gsp_events_write_log(uint64_t *ev, int64_t n, const char *path);
 
 /* ------------------------------------------------------------------------------------
+ * Detection ledger: the event records folded per member on the device.  While a ledger is
+ * open, every tick ends with one fold over each local shard's event ring: the tick's records
+ * are reduced into the arrays below and the ring is emptied, so it never fills across ticks and
+ * no record leaves the device before get.  With no ledger open nothing is added to step.
+ * crash[x] is the engine's failure schedule (INT32_MAX: never); by the census's aliveness rule
+ * x is alive at t while t <= crash[x].  Per member x, n elements each:
+ *   first_remove / last_remove  smallest / largest t over remove records of x with t > crash[x],
+ *                               -1: none
+ *   removers                    how many such records
+ *   false_removes / first_false remove records of x with t <= crash[x] (x was alive at t): how
+ *                               many, and the smallest t (-1: none)
+ *   revivals                    join records of x with t > crash[x]
+ *   evicts                      evict records of x (all 0 in the full view)
+ *   state                       as in the census, at the engine's tick T
+ * by_tick[t][4] for t < min(by_tick_cap, T + 1): the true removes, false removes, revivals and
+ * evictions whose record tick is t.  Any out pointer may be NULL.
+ * open     GSP_ERR_INVALID when the engine does not record removes (params.events) or a ledger
+ *          is open.  Folds what the ring holds at that moment -- every record since the last
+ *          drain: opened at tick 0 a ledger covers the run, opened after a drain at tick T it
+ *          covers the ticks > T.  Kinds the engine does not record count 0.
+ * fold     each fold adds max(0, counter - stripe capacity) per stripe to `lost`, the records a
+ *          full stripe refused within that tick: records + lost = the records the tick kernels
+ *          made.  gsp_*_drain_events is unchanged; after a step it finds an empty ring.
+ * get      synchronises (a pending capacity error returns GSP_ERR_CAPACITY as the other reads do).
+ * close    frees the ledger and leaves the ring empty; it fills and drains as before from then on.
+ * The result is the same for every layout and number of shards.  With a communicator open, get
+ * and close are COLLECTIVE (get all-reduces MIN / MAX / SUM into a staging buffer).
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t tick, n;
+    int32_t open_tick;     /* the engine's tick at open                                     */
+    int32_t kinds;         /* the kinds the engine records: an OR of GSP_EVENTS_JOIN / REMOVE /
+                              EVICT                                                         */
+    int32_t ticks_folded;  /* ticks stepped since open (one fold each)                      */
+    int32_t reserved;
+    int64_t records;       /* records folded                                                */
+    int64_t lost;          /* records a full stripe refused                                 */
+    int64_t true_removes, false_removes, joins, revivals, evicts;
+    double kernel_ms;      /* HIP events around every fold since open, collected at sync (0:
+                              timing off)                                                   */
+} gsp_detect_info;
+
+int gsp_scale_detect_open(gsp_scale *s);
+int gsp_scale_detect_get(gsp_scale *s, int32_t *first_remove, int32_t *last_remove,
+                         uint32_t *removers, uint32_t *false_removes, int32_t *first_false,
+                         uint32_t *revivals, uint32_t *evicts, uint8_t *state, uint64_t *by_tick,
+                         int32_t by_tick_cap, gsp_detect_info *info);
+int gsp_scale_detect_close(gsp_scale *s);
+
+/* ------------------------------------------------------------------------------------
  * PARTIAL-VIEW engine (BASELINE config 5): every node keeps at most `view` member entries
  * (id, hb, ts) sorted by id; a receiver merges at most `inbox` messages per tick (1..7,
  * ascending sender; the rest are counted as overflow) -- or, with inbox = 0, every message it
@@ -689,6 +739,13 @@ int gsp_pview_rumor_get(gsp_pview *s, int32_t rumor, int32_t *heard, uint8_t *st
 int gsp_pview_rumor_close(gsp_pview *s);
 /* As gsp_scale_drain_events (join / remove / evict records). */
 int gsp_pview_drain_events(gsp_pview *s, uint64_t *buf, int64_t cap, int64_t *n, int64_t *lost);
+/* As gsp_scale_detect_* ("Detection ledger" above), with evict records. */
+int gsp_pview_detect_open(gsp_pview *s);
+int gsp_pview_detect_get(gsp_pview *s, int32_t *first_remove, int32_t *last_remove,
+                         uint32_t *removers, uint32_t *false_removes, int32_t *first_false,
+                         uint32_t *revivals, uint32_t *evicts, uint8_t *state, uint64_t *by_tick,
+                         int32_t by_tick_cap, gsp_detect_info *info);
+int gsp_pview_detect_close(gsp_pview *s);
 /* Test diagnostics: the rows the tick kernels of tick t ran, summed over the shards held here
  * -- every row exactly once in every launch form, so it equals the rows held.  Needs the
  * environment variable GSP_TEST_PV_COUNT_ROWS=1 at create (else GSP_ERR_INVALID). */

@@ -162,8 +162,29 @@ _DETECT_GET = (ctypes.c_int, [ctypes.c_void_p, P(c_int32), P(c_int32), P(ctypes.
                               P(ctypes.c_uint32), P(c_int32), P(ctypes.c_uint32), P(ctypes.c_uint32),
                               P(ctypes.c_uint8), P(c_uint64), c_int32, P(GspDetectInfo)])
 
+
+class GspTrafficInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("open_tick", c_int32), ("ticks_counted", c_int32),
+                ("n_watch", c_int32), ("reserved", c_int32), ("sent", c_int64), ("recv", c_int64),
+                ("merged", c_int64), ("lost", c_int64), ("entries", c_int64), ("overflow", c_int64),
+                ("max_fanin", c_int32), ("max_fanin_node", c_int32), ("kernel_ms", ctypes.c_double)]
+
+
+_TRAFFIC_OPEN = (ctypes.c_int, [ctypes.c_void_p, P(c_int32), c_int32])
+_TRAFFIC_GET = (ctypes.c_int, [ctypes.c_void_p] + [P(ctypes.c_uint32)] * 4 + [P(c_uint64), P(ctypes.c_uint32),
+                               P(c_int32), P(ctypes.c_uint8), P(c_uint64), P(c_uint64), P(ctypes.c_uint32),
+                               c_int32, P(GspTrafficInfo)])
+_TRAFFIC_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
+
 # name -> (restype, argtypes); every name here must be exported (tests check it)
 SIGNATURES = {
+    "gsp_scale_traffic_open": _TRAFFIC_OPEN,
+    "gsp_scale_traffic_get": _TRAFFIC_GET,
+    "gsp_scale_traffic_close": _TRAFFIC_CLOSE,
+    "gsp_pview_traffic_open": _TRAFFIC_OPEN,
+    "gsp_pview_traffic_get": _TRAFFIC_GET,
+    "gsp_pview_traffic_close": _TRAFFIC_CLOSE,
+    "gsp_traffic_write_msgcount": (ctypes.c_int, [ctypes.c_char_p, P(c_int32), P(c_int32), c_int32, c_int32]),
     "gsp_scale_detect_open": _DETECT_OPEN,
     "gsp_scale_detect_get": _DETECT_GET,
     "gsp_scale_detect_close": _DETECT_OPEN,

@@ -1,4 +1,5 @@
-// gossip_protocol_amd/csrc/capi_common.cpp -- status strings, Params parsing, device count.
+// gossip_protocol_amd/csrc/capi_common.cpp -- status strings, Params parsing, device count, the
+// msgcount.log formatter.
 #include <cstdio>
 #include <cstring>
 
@@ -18,6 +19,28 @@ void set_error(const char *fmt, ...) {
     g_error = buf;
 }
 const char *get_error() { return g_error.c_str(); }
+
+// EmulNet::ENcleanup's loop (EmulNet.cpp:195-216): row i of sent / recv is printed as node i + 1,
+// ten pairs per line, node 67 in its "special" layout.
+void write_msgcount_rows(FILE *f, const int32_t *sent, const int32_t *recv, int32_t nodes, int32_t ticks) {
+    for (int32_t id = 1; id <= nodes; ++id) {
+        const int32_t *srow = sent + size_t(id - 1) * size_t(ticks), *rrow = recv + size_t(id - 1) * size_t(ticks);
+        std::fprintf(f, "node %3d ", id);
+        uint32_t st = 0, rt = 0;
+        for (int32_t j = 0; j < ticks; ++j) {
+            const int32_t a = srow[j], c = rrow[j];
+            st += uint32_t(a);
+            rt += uint32_t(c);
+            if (id == 67) {
+                std::fprintf(f, "special %4d %4d %4d\n", j, a, c);
+            } else {
+                std::fprintf(f, " (%4d, %4d)", a, c);
+                if (j % 10 == 9) std::fprintf(f, "\n         ");
+            }
+        }
+        std::fprintf(f, "\nnode %3d sent_total %6u  recv_total %6u\n\n", id, st, rt);
+    }
+}
 }  // namespace gsp
 
 extern "C" {
@@ -40,6 +63,17 @@ int gsp_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+
+int gsp_traffic_write_msgcount(const char *path, const int32_t *sent, const int32_t *recv, int32_t nodes,
+                               int32_t ticks) {
+    GSP_REQUIRE(path && nodes >= 0 && ticks >= 0 && ((sent && recv) || nodes == 0 || ticks == 0),
+                GSP_ERR_INVALID, "gsp_traffic_write_msgcount: NULL argument, or nodes=%d / ticks=%d", nodes, ticks);
+    FILE *f = std::fopen(path, "w");
+    GSP_REQUIRE(f, GSP_ERR_IO, "gsp_traffic_write_msgcount: cannot write %s", path);
+    gsp::write_msgcount_rows(f, sent, recv, nodes, ticks);
+    GSP_REQUIRE(std::fclose(f) == 0, GSP_ERR_IO, "gsp_traffic_write_msgcount: writing %s failed", path);
+    return GSP_OK;
 }
 
 int gsp_params_default(gsp_params *out) {

@@ -12,6 +12,10 @@ namespace gsp {
 void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 const char *get_error();
 
+// msgcount.log rows (capi_common.cpp): the one formatter behind gsp_write_msgcount and
+// gsp_traffic_write_msgcount
+void write_msgcount_rows(FILE *f, const int32_t *sent, const int32_t *recv, int32_t nodes, int32_t ticks);
+
 // Returns from the enclosing C-ABI function with GSP_ERR_HIP on failure.
 #define GSP_HIP(call)                                                                   \
     do {                                                                                \

@@ -6,8 +6,8 @@
 // only those members.  Here: the stream, the timing-event pool, the failure / join schedule,
 // the communicator, the capacity flag and its host mirror, the single-shard CSR build, the
 // JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census,
-// of the overlay reach, of the rumor trace and of the detection ledger, and the C-ABI bodies that
-// are the same code.
+// of the overlay reach, of the rumor trace, of the detection ledger and of the traffic ledger, and
+// the C-ABI bodies that are the same code.
 // Tables, tick arguments, kernels launched and test knobs stay with each engine.
 #pragma once
 #include <rccl/rccl.h>
@@ -27,6 +27,7 @@
 #include "rowx_host.hpp"
 #include "rumor_kernels.hpp"
 #include "scale_kernels.hpp"
+#include "traffic_kernels.hpp"
 
 namespace gsp {
 
@@ -145,6 +146,34 @@ struct DetectBufs {
     }
 };
 
+// The traffic ledger (gsp_*_traffic_*, traffic_kernels.hpp), allocated by open and freed by close,
+// shared by every local shard.  arr holds the four per-node counters and, behind them, the watch
+// rows; `red` / `red64` stage the all-reduced buffers of a get across row-shard ranks, so the
+// device state itself is never summed twice.
+struct TrafficBufs {
+    bool open = false;
+    int form = kTrafficFromSlots;                // GSP_TEST_TRAFFIC_FORM=0|1 (tests, A/B) overrides
+    int32_t open_tick = 0, ticks_counted = 0, n_watch = 0;
+    int32_t sent_done = -1;                      // from-CSR form: the tick whose sends a get folded
+    double kernel_ms = 0.0;
+    DevBuf<uint32_t> arr, red;                   // [kTrFields][n], then watch[n_watch][span][2]
+    DevBuf<unsigned long long> wide, red64;      // TrafficLayout
+    DevBuf<int32_t> watch_slot, psize;           // [n] each; psize: the partial view's payload sizes
+    std::vector<uint32_t> h_arr;
+    std::vector<unsigned long long> h_wide;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // timed passes not yet collected
+
+    void release() {
+        for (auto *b : {&arr, &red}) b->release();
+        for (auto *b : {&wide, &red64}) b->release();
+        for (auto *b : {&watch_slot, &psize}) b->release();
+        open = false;
+        open_tick = ticks_counted = n_watch = 0;
+        sent_done = -1;
+        kernel_ms = 0.0;
+    }
+};
+
 struct EngineCore {
     int device = 0;
     hipStream_t st = nullptr;
@@ -170,6 +199,7 @@ struct EngineCore {
     ReachBufs reach;
     RumorBufs rumor;
     DetectBufs detect;
+    TrafficBufs traffic;
 
     void recycle(const Timed &t) {     // a tick's three events back to the pool
         for (hipEvent_t e : {t.a, t.b, t.c}) free_events.push_back(e);
@@ -254,6 +284,9 @@ inline void engine_close(EngineCore &c) {
     for (auto &e : c.detect.pending) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
     c.detect.pending.clear();
     c.detect.release();
+    for (auto &e : c.traffic.pending) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+    c.traffic.pending.clear();
+    c.traffic.release();
     c.rowx.release();
     if (c.h_err) (void)hipHostFree(c.h_err);
     if (c.st) (void)hipStreamDestroy(c.st);
@@ -442,6 +475,20 @@ int check_err(E *s, int32_t drain_bit) {
     return mirrored_err(s, drain_bit);
 }
 
+// the traffic ledger's timed passes into its kernel_ms (waits for their events)
+inline int traffic_collect(EngineCore &c) {
+    for (auto &e : c.traffic.pending) {
+        float ms = 0.f;
+        GSP_HIP(hipEventSynchronize(e.second));
+        GSP_HIP(hipEventElapsedTime(&ms, e.first, e.second));
+        c.traffic.kernel_ms += ms;
+        c.free_events.push_back(e.first);
+        c.free_events.push_back(e.second);
+    }
+    c.traffic.pending.clear();
+    return GSP_OK;
+}
+
 // the timed ticks into perf (waits for their events); row layout: the exchanges' byte counts
 inline int collect_timing(EngineCore &c) {
     for (auto &t : c.pending) {
@@ -473,6 +520,7 @@ inline int collect_timing(EngineCore &c) {
         c.free_events.push_back(e.second);
     }
     c.detect.pending.clear();
+    if (int rc = traffic_collect(c)) return rc;
     if (c.rowmode)
         if (int rc = rowx_collect(c.rowx, &c.perf.xgmi_bytes)) return rc;
     return GSP_OK;
@@ -1023,6 +1071,247 @@ int detect_get(E &s, const char *fn, int32_t *first_remove, int32_t *last_remove
                                 int64_t(tot[kDetRevived]), int64_t(tot[kDetEvicted]),
                                 s.timing ? b.kernel_ms : 0.0};
     }
+    return GSP_OK;
+}
+
+// ---- the traffic ledger (gossip.h "Traffic ledger", traffic_kernels.hpp) ----
+// Who computes what, as for the rumor trace: without row shards every engine holds the job's whole
+// receiver CSR and every send slot in local[0] and runs all n rows from it, so ranks need no
+// exchange; row shards write their own rows of the shared ledger, and across ranks a get
+// all-reduces the buffers (SUM; MAX for the peaks) into staging.
+
+template <class E>
+int traffic_open(E &s, const char *fn, const int32_t *watch, int32_t n_watch, bool own_sizes) {
+    TrafficBufs &b = s.traffic;
+    GSP_REQUIRE(!b.open, GSP_ERR_INVALID, "%s: a ledger is already open (since tick %d)", fn, b.open_tick);
+    GSP_REQUIRE(n_watch >= 0 && n_watch <= kTrMaxWatch && (watch || n_watch == 0), GSP_ERR_INVALID,
+                "%s: n_watch=%d outside [0,%d], or no ids", fn, n_watch, kTrMaxWatch);
+    const size_t n = size_t(s.p.n), span = size_t(s.p.max_ticks) + 1;
+    std::vector<int32_t> slot(n, -1);
+    for (int32_t w = 0; w < n_watch; ++w) {
+        GSP_REQUIRE(watch[w] >= 0 && watch[w] < s.p.n, GSP_ERR_INVALID, "%s: watch[%d]=%d outside [0,%d)",
+                    fn, w, watch[w], s.p.n);
+        GSP_REQUIRE(slot[size_t(watch[w])] < 0, GSP_ERR_INVALID, "%s: watch[%d]=%d is listed twice", fn, w,
+                    watch[w]);
+        slot[size_t(watch[w])] = w;
+    }
+    const TrafficLayout L{n, span};
+    const size_t words = size_t(kTrFields) * n + std::max<size_t>(1, size_t(n_watch)) * span * 2;
+    GSP_HIP(b.arr.alloc(words));
+    GSP_HIP(b.wide.alloc(L.total()));
+    GSP_HIP(b.watch_slot.alloc(n));
+    if (own_sizes) GSP_HIP(b.psize.alloc(n));
+    if (s.rowmode && s.comm) {
+        GSP_HIP(b.red.alloc(words));
+        GSP_HIP(b.red64.alloc(L.total()));
+    }
+    GSP_HIP(hipMemsetAsync(b.arr.p, 0, words * 4, s.st));
+    GSP_HIP(hipMemsetAsync(b.wide.p, 0, L.total() * 8, s.st));
+    GSP_HIP(hipMemcpyAsync(b.watch_slot.p, slot.data(), n * 4, hipMemcpyHostToDevice, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));       // open is between steps: the map's copy is done on return
+    b.form = kTrafficFromSlots;
+    if (const char *f = std::getenv("GSP_TEST_TRAFFIC_FORM")) b.form = std::atoi(f) ? kTrafficFromCsr : kTrafficFromSlots;
+    b.open_tick = s.tick;
+    b.ticks_counted = 0;
+    b.n_watch = n_watch;
+    b.sent_done = -1;
+    b.kernel_ms = 0.0;
+    b.open = true;
+    return GSP_OK;
+}
+
+template <class E>
+int traffic_close(E &s, const char *fn) {
+    TrafficBufs &b = s.traffic;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no ledger is open", fn);
+    GSP_HIP(hipStreamSynchronize(s.st));           // no queued launch still uses the buffers
+    for (auto &e : b.pending) {
+        s.free_events.push_back(e.first);
+        s.free_events.push_back(e.second);
+    }
+    b.pending.clear();
+    b.release();
+    return GSP_OK;
+}
+
+// a timed span of ledger launches on the engine's stream
+template <class E, class Body>
+int traffic_timed(E *s, Body body) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (s->timing) {
+        e0 = s->event();
+        e1 = s->event();
+        GSP_HIP(hipEventRecord(e0, s->st));
+    }
+    if (int rc = body()) return rc;
+    if (s->timing) {
+        GSP_HIP(hipEventRecord(e1, s->st));
+        s->traffic.pending.emplace_back(e0, e1);
+    }
+    return GSP_OK;
+}
+
+// The receiver pass of tick t, on the engine's stream with no host wait: called where the receiver
+// CSR of t is complete and before the tick kernels.  prep() queues what the sizes need (the
+// partial view's count pass or length copies); fill(shard, args) adds what only the engine knows:
+// psize, intro_list and the partial view's receipt records.
+template <class E, class Prep, class Fill>
+int traffic_step_recv(E *s, int32_t t, Prep prep, Fill fill) {
+    TrafficBufs &b = s->traffic;
+    const size_t n = size_t(s->p.n);
+    // the from-CSR form charges the sends of t - 1 here, unless a get has folded them already
+    const bool charge = b.form == kTrafficFromCsr && t - 1 > b.open_tick && b.sent_done != t - 1;
+    return traffic_timed(s, [&]() -> int {
+        if (int rc = prep()) return rc;
+        for (auto &sh : s->local) {
+            if (!s->rowmode && &sh != &s->local[0]) continue;   // one CSR of all n rows
+            TrafficRecvArgs a{};
+            a.n = s->p.n;
+            a.tick = t;
+            a.span = s->p.max_ticks + 1;
+            a.row0 = sh.row0;
+            a.rows = sh.rows;
+            a.off = sh.off.p;
+            a.csr_src = sh.csr_src.p;
+            a.fail_tick = sh.fail_tick.p;
+            a.start_tick = s->joins ? sh.start_tick.p : nullptr;
+            a.intro_list = s->p.policy.intro_list;
+            a.form = charge ? kTrafficFromCsr : kTrafficFromSlots;
+            a.arr = b.arr.p;
+            a.wide = b.wide.p;
+            a.watch_slot = b.watch_slot.p;
+            a.watch = b.arr.p + size_t(kTrFields) * n;
+            fill(sh, a);
+            GSP_HIP(launch_traffic_recv(a, s->st));
+        }
+        return GSP_OK;
+    });
+}
+
+// The sender pass of tick t: the send slots and, behind them, node 0's delivered JOINREPs (to the
+// joiners of t + 1).  Called once every writer of the tick's slots has been queued.
+template <class E>
+int traffic_send_pass(E *s, int32_t t) {
+    TrafficBufs &b = s->traffic;
+    const size_t n = size_t(s->p.n);
+    const int64_t cnt = s->joins ? s->plan.count(t + 1) : 0;
+    return traffic_timed(s, [&]() -> int {
+        for (auto &sh : s->local) {
+            if (!s->rowmode && &sh != &s->local[0]) continue;   // local[0] holds every slot
+            TrafficSendArgs a{};
+            a.n = s->p.n;
+            a.tick = t;
+            a.span = s->p.max_ticks + 1;
+            a.row0 = sh.row0;
+            a.rows = sh.rows;
+            a.fanout = s->p.fanout;
+            a.out_dst = sh.out_dst.p;
+            a.arr = b.arr.p;
+            a.wide = b.wide.p;
+            a.watch_slot = b.watch_slot.p;
+            a.watch = b.arr.p + size_t(kTrFields) * n;
+            GSP_HIP(launch_traffic_send(a, s->st));
+            if (cnt == 0) continue;
+            TrafficJoinArgs j{};
+            j.n = a.n;
+            j.tick = t;
+            j.span = a.span;
+            j.ok = sh.join_ok.p + s->plan.first(t + 1);   // a row shard flags the joiners it holds
+            j.count = int32_t(cnt);
+            j.arr = a.arr;
+            j.wide = a.wide;
+            j.watch_slot = a.watch_slot;
+            j.watch = a.watch;
+            GSP_HIP(launch_traffic_join(j, s->st));
+        }
+        return GSP_OK;
+    });
+}
+
+// the end of one stepped tick (the from-CSR form takes the sends from the next tick's CSR)
+template <class E>
+int traffic_step_send(E *s, int32_t t) {
+    ++s->traffic.ticks_counted;
+    if (s->traffic.form == kTrafficFromCsr) return GSP_OK;
+    return traffic_send_pass(s, t);
+}
+
+// The ledger at the engine's tick T, after the engine has synchronised and reported any pending
+// capacity error.
+template <class E>
+int traffic_get(E &s, const char *fn, uint32_t *sent, uint32_t *recv, uint32_t *merged, uint32_t *lost,
+                uint64_t *entries_in, uint32_t *peak_recv, int32_t *peak_tick, uint8_t *state,
+                uint64_t *by_tick, uint64_t *fanin, uint32_t *watch, int32_t tick_cap,
+                gsp_traffic_info *info) {
+    TrafficBufs &b = s.traffic;
+    GSP_REQUIRE(b.open, GSP_ERR_INVALID, "%s: no ledger is open", fn);
+    GSP_REQUIRE(tick_cap >= 0 || !(by_tick || fanin || watch), GSP_ERR_INVALID, "%s: tick_cap=%d", fn, tick_cap);
+    const size_t n = size_t(s.p.n), span = size_t(s.p.max_ticks) + 1;
+    const int32_t T = s.tick;
+    const TrafficLayout L{n, span};
+    const size_t words = size_t(kTrFields) * n + std::max<size_t>(1, size_t(b.n_watch)) * span * 2;
+    if (b.form == kTrafficFromCsr && T > b.open_tick && b.sent_done != T) {
+        if (int rc = traffic_send_pass(&s, T)) return rc;      // the last tick's sends are in no CSR yet
+        b.sent_done = T;
+    }
+    const uint32_t *d_arr = b.arr.p;
+    const unsigned long long *d_wide = b.wide.p;
+    if (s.rowmode && s.comm) {
+        GSP_NCCL(ncclAllReduce(b.arr.p, b.red.p, words, ncclUint32, ncclSum, s.comm, s.st));
+        GSP_NCCL(ncclAllReduce(b.wide.p, b.red64.p, L.added(), ncclUint64, ncclSum, s.comm, s.st));
+        GSP_NCCL(ncclAllReduce(b.wide.p + L.peak(), b.red64.p + L.peak(), L.total() - L.added(), ncclUint64,
+                               ncclMax, s.comm, s.st));
+        d_arr = b.red.p;
+        d_wide = b.red64.p;
+    }
+    b.h_arr.resize(words);
+    b.h_wide.resize(L.total());
+    GSP_HIP(hipMemcpyAsync(b.h_arr.data(), d_arr, words * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipMemcpyAsync(b.h_wide.data(), d_wide, L.total() * 8, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    if (int rc = traffic_collect(s)) return rc;                // a fold queued by this get
+    const uint32_t *h = b.h_arr.data();
+    const unsigned long long *w = b.h_wide.data();
+    unsigned long long best = 0ull;
+    int32_t best_node = -1;
+    for (size_t x = 0; x < n; ++x) {
+        const unsigned long long pk = w[L.peak() + x];
+        if (pk > best) {
+            best = pk;
+            best_node = int32_t(x);
+        }
+        if (sent) sent[x] = h[size_t(kTrSent) * n + x];
+        if (recv) recv[x] = h[size_t(kTrRecv) * n + x];
+        if (merged) merged[x] = h[size_t(kTrMerged) * n + x];
+        if (lost) lost[x] = h[size_t(kTrLost) * n + x];
+        if (entries_in) entries_in[x] = w[L.entries() + x];
+        if (peak_recv) peak_recv[x] = uint32_t(pk >> 32);
+        if (peak_tick) peak_tick[x] = pk ? int32_t(~uint32_t(pk)) : -1;
+        if (state) state[x] = T < s.h_start[x] ? 0 : T <= s.h_fail[x] ? 1 : 2;
+    }
+    unsigned long long tot[kTrSums] = {0};
+    for (int32_t t = 0; t <= T; ++t) {
+        for (int c = 0; c < kTrSums; ++c) tot[c] += w[L.sums() + size_t(t) * kTrSums + c];
+        if (t >= tick_cap) continue;
+        if (by_tick) {
+            for (int c = 0; c < kTrSums; ++c) by_tick[size_t(t) * 6 + c] = w[L.sums() + size_t(t) * kTrSums + c];
+            by_tick[size_t(t) * 6 + 5] = w[L.tmax() + size_t(t)];
+        }
+        if (fanin)
+            for (int c = 0; c < kTrBuckets; ++c)
+                fanin[size_t(t) * kTrBuckets + c] = w[L.fanin() + size_t(t) * kTrBuckets + c];
+        if (watch)
+            for (int32_t i = 0; i < b.n_watch; ++i)
+                for (int c = 0; c < 2; ++c)
+                    watch[(size_t(i) * size_t(tick_cap) + size_t(t)) * 2 + c] =
+                        h[size_t(kTrFields) * n + (size_t(i) * span + size_t(t)) * 2 + c];
+    }
+    if (info)
+        *info = gsp_traffic_info{T, s.p.n, b.open_tick, b.ticks_counted, b.n_watch, 0,
+                                 int64_t(tot[kTrSumSent]), int64_t(tot[kTrSumRecv]), int64_t(tot[kTrSumMerged]),
+                                 int64_t(tot[kTrSumLost]), int64_t(tot[kTrSumEntries]),
+                                 int64_t(tot[kTrSumRecv] - tot[kTrSumMerged]), int32_t(best >> 32), best_node,
+                                 s.timing ? b.kernel_ms : 0.0};
     return GSP_OK;
 }
 

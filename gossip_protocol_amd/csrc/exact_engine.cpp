@@ -1101,22 +1101,8 @@ int gsp_write_msgcount(gsp_engine *e, const char *path, int32_t tick) {
     if (int rc = gsp_counters(e, sent.data(), recv.data(), tick)) return rc;
     FILE *f = std::fopen(path, "w");
     GSP_REQUIRE(f, GSP_ERR_IO, "gsp_write_msgcount: cannot write %s", path);
-    for (int32_t id = 1; id <= N; ++id) {
-        std::fprintf(f, "node %3d ", id);
-        uint32_t st = 0, rt = 0;
-        for (int32_t j = 0; j < tick; ++j) {
-            const int32_t a = sent[size_t(id) * tick + j], c = recv[size_t(id) * tick + j];
-            st += uint32_t(a);
-            rt += uint32_t(c);
-            if (id == 67) {
-                std::fprintf(f, "special %4d %4d %4d\n", j, a, c);
-            } else {
-                std::fprintf(f, " (%4d, %4d)", a, c);
-                if (j % 10 == 9) std::fprintf(f, "\n         ");
-            }
-        }
-        std::fprintf(f, "\nnode %3d sent_total %6u  recv_total %6u\n\n", id, st, rt);
-    }
+    // the counters' row 0 belongs to no node: node id is row id
+    gsp::write_msgcount_rows(f, sent.data() + tick, recv.data() + tick, N, tick);
     std::fclose(f);
     return GSP_OK;
 }

@@ -376,6 +376,37 @@ int pview_build(const gsp_pview_params *p, int device, int32_t shards, int32_t r
     return GSP_OK;
 }
 
+// What a GOSSIP sent at t - 1 carried, per sender, into the ledger's psize[n] (an open ledger
+// only).  Without TFAIL that is the previous view's length: one shard reads its len directly (no
+// launch), row shards copy theirs into place.  With TFAIL one streaming count pass per shard leaves
+// out the suspects of t - 1.  Across ranks the n words are summed (every rank writes its rows only).
+int traffic_sizes(gsp_pview *s, int32_t t) {
+    int32_t *psize = s->traffic.psize.p;
+    if (!psize) return GSP_OK;
+    const size_t n = size_t(s->p.n);
+    const bool ranks = s->rowmode && s->comm;
+    if (ranks) GSP_HIP(hipMemsetAsync(psize, 0, n * 4, s->st));
+    for (PvShard &sh : s->local) {
+        if (s->p.tfail > 0) {
+            gsp::TrafficSizeArgs a{};
+            a.tick = t - 1;
+            a.tfail = s->p.tfail;
+            a.view = s->p.view;
+            a.row0 = sh.row0;
+            a.rows = sh.rows;
+            a.table = sh.table[(t + 1) & 1].p;
+            a.len = sh.len[(t + 1) & 1].p;
+            a.psize = psize;
+            GSP_HIP(gsp::launch_traffic_sizes(a, s->st));
+        } else {
+            GSP_HIP(hipMemcpyAsync(psize + sh.row0, sh.len[(t + 1) & 1].p, size_t(sh.rows) * 4,
+                                   hipMemcpyDeviceToDevice, s->st));
+        }
+    }
+    if (ranks) GSP_NCCL(ncclAllReduce(psize, psize, n, ncclInt32, ncclSum, s->comm, s->st));
+    return GSP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -476,6 +507,13 @@ int gsp_pview_step(gsp_pview *s, int32_t ticks) {
                     a.rc_info = s->drain ? nullptr : sh.rc_info.p;
                     a.rc_src = s->drain ? nullptr : sh.rc_src.p;
                 })) return rc;
+        if (s->traffic.open)     // payload sizes: the previous views' lengths, cut by TFAIL
+            if (int rc = gsp::traffic_step_recv(s, t, [&] { return traffic_sizes(s, t); },
+                                                [&](PvShard &sh, gsp::TrafficRecvArgs &a) {
+                    a.psize = s->traffic.psize.p ? s->traffic.psize.p : sh.len[(t + 1) & 1].p;
+                    a.rc_info = s->drain ? nullptr : sh.rc_info.p;
+                    a.rc_src = s->drain ? nullptr : sh.rc_src.p;
+                })) return rc;
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
         for (PvShard &sh : s->local) {
             gsp::PviewTickArgs ta = s->args(sh, t);
@@ -501,6 +539,8 @@ int gsp_pview_step(gsp_pview *s, int32_t ticks) {
         if (s->detect.open)      // the hub kernel's stream has joined back: fold, empty the ring
             if (int rc = gsp::detect_step(s)) return rc;
         if (int rc = gsp::join_sends(s, t, join_form(s))) return rc;
+        if (s->traffic.open)     // the tick's send slots and JOINREP flags are final
+            if (int rc = gsp::traffic_step_send(s, t)) return rc;
         s->tick = t;
         s->perf.ticks++;
     }
@@ -693,6 +733,30 @@ int gsp_pview_detect_close(gsp_pview *s) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_detect_close: NULL");
     GSP_HIP(hipSetDevice(s->device));
     return gsp::detect_close(*s, "gsp_pview_detect_close");
+}
+
+// Traffic ledger (engine_host.hpp traffic_*): the ledger keeps its own psize[n] when the sizes
+// are not one shard's plain row lengths (TFAIL, or row shards).
+int gsp_pview_traffic_open(gsp_pview *s, const int32_t *watch, int32_t n_watch) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_traffic_open: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::traffic_open(*s, "gsp_pview_traffic_open", watch, n_watch, s->p.tfail > 0 || s->rowmode);
+}
+
+int gsp_pview_traffic_get(gsp_pview *s, uint32_t *sent, uint32_t *recv, uint32_t *merged, uint32_t *lost,
+                          uint64_t *entries_in, uint32_t *peak_recv, int32_t *peak_tick, uint8_t *state,
+                          uint64_t *by_tick, uint64_t *fanin, uint32_t *watch, int32_t tick_cap,
+                          gsp_traffic_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_traffic_get: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::traffic_get(*s, "gsp_pview_traffic_get", sent, recv, merged, lost, entries_in, peak_recv,
+                            peak_tick, state, by_tick, fanin, watch, tick_cap, info);
+}
+
+int gsp_pview_traffic_close(gsp_pview *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_traffic_close: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::traffic_close(*s, "gsp_pview_traffic_close");
 }
 
 int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out) {

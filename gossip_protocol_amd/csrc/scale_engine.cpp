@@ -551,6 +551,10 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
         if (int rc = gsp::join_scatter(s, t, s->shared)) return rc;
         if (s->rumor.open)       // the CSR of t is complete; the tick kernels may sort it in place
             if (int rc = gsp::rumor_step(s, t, [](Shard &, gsp::RumorTickArgs &) {})) return rc;
+        if (s->traffic.open)     // payload sizes: the counts the tick kernels add to merges
+            if (int rc = gsp::traffic_step_recv(s, t, [] { return GSP_OK; }, [&](Shard &sh, gsp::TrafficRecvArgs &a) {
+                    a.psize = s->owner(sh).cnt_total[(t + 1) & 1].p;
+                })) return rc;
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
         for (Shard &sh : s->local)
             GSP_HIP(gsp::launch_scale_tick(s->args(sh, t), s->sliced, s->merge, s->st));
@@ -573,6 +577,8 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
         if (s->rowmode)
             if (int rc = exchange_row_counts(s, t)) return rc;
         if (int rc = gsp::join_sends(s, t, join_form(s))) return rc;
+        if (s->traffic.open)     // the tick's send slots and JOINREP flags are final
+            if (int rc = gsp::traffic_step_send(s, t)) return rc;
         s->tick = t;
         s->perf.ticks++;
     }
@@ -800,6 +806,29 @@ int gsp_scale_detect_close(gsp_scale *s) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_detect_close: NULL");
     GSP_HIP(hipSetDevice(s->device));
     return gsp::detect_close(*s, "gsp_scale_detect_close");
+}
+
+// Traffic ledger (engine_host.hpp traffic_*): a GOSSIP carries its sender's member count.
+int gsp_scale_traffic_open(gsp_scale *s, const int32_t *watch, int32_t n_watch) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_traffic_open: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::traffic_open(*s, "gsp_scale_traffic_open", watch, n_watch, false);
+}
+
+int gsp_scale_traffic_get(gsp_scale *s, uint32_t *sent, uint32_t *recv, uint32_t *merged, uint32_t *lost,
+                          uint64_t *entries_in, uint32_t *peak_recv, int32_t *peak_tick, uint8_t *state,
+                          uint64_t *by_tick, uint64_t *fanin, uint32_t *watch, int32_t tick_cap,
+                          gsp_traffic_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_traffic_get: NULL");
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::traffic_get(*s, "gsp_scale_traffic_get", sent, recv, merged, lost, entries_in, peak_recv,
+                            peak_tick, state, by_tick, fanin, watch, tick_cap, info);
+}
+
+int gsp_scale_traffic_close(gsp_scale *s) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_traffic_close: NULL");
+    GSP_HIP(hipSetDevice(s->device));
+    return gsp::traffic_close(*s, "gsp_scale_traffic_close");
 }
 
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {

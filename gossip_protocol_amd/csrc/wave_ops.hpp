@@ -47,6 +47,18 @@ __device__ __forceinline__ uint32_t wave_or32(uint32_t x) {
     return lane_of(x, 63);
 }
 
+// unsigned maximum of x over the wave, in every lane: the same six steps with max (a lane left
+// out takes 0, the identity)
+__device__ __forceinline__ uint32_t wave_max32(uint32_t x) {
+    x = max(x, dpp_take<0x111>(x));
+    x = max(x, dpp_take<0x112>(x));
+    x = max(x, dpp_take<0x114>(x));
+    x = max(x, dpp_take<0x118>(x));
+    x = max(x, dpp_take<0x142, 0xA>(x));
+    x = max(x, dpp_take<0x143, 0xC>(x));
+    return lane_of(x, 63);
+}
+
 __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) { return lane_of(wave_incl_scan(v), 63); }
 
 // 64-bit wave sum (mod 2^64) from three 32-bit scans: the low word in two 16-bit halves (each

@@ -165,6 +165,24 @@ class PviewEngine:
         """Free the ledger; the ring is left empty and fills and drains as before.  Collective."""
         check(lib().gsp_pview_detect_close(self._h), "gsp_pview_detect_close")
 
+    def traffic_open(self, watch=None):
+        """Open the traffic ledger (traffic.py): from now on every tick counts, on the device,
+        what each node sends, is sent, merges and loses to dead receivers.  watch: up to 1,024
+        distinct node ids whose (sent, recv) are kept for every tick."""
+        from . import traffic
+        self._traffic_watch = traffic.open_(lib().gsp_pview_traffic_open, self._h, watch,
+                                            "gsp_pview_traffic_open")
+
+    def traffic(self):
+        """traffic.Traffic of the open ledger at the current tick.  Collective."""
+        from . import traffic
+        return traffic.get(lib().gsp_pview_traffic_get, self._h, self.params,
+                           getattr(self, "_traffic_watch", ()), "gsp_pview_traffic_get")
+
+    def traffic_close(self):
+        """Free the ledger; step is back to the launches it makes without one.  Collective."""
+        check(lib().gsp_pview_traffic_close(self._h), "gsp_pview_traffic_close")
+
     def drain_events(self):
         """(records, lost) since the last drain (events=True); see _lib.split_events."""
         return _lib.drain_events(lib().gsp_pview_drain_events, self._h)

@@ -662,6 +662,72 @@ int gsp_scale_detect_get(gsp_scale *s, int32_t *first_remove, int32_t *last_remo
 int gsp_scale_detect_close(gsp_scale *s);
 
 /* ------------------------------------------------------------------------------------
+ * Traffic ledger: per-node message and payload load, counted on the device -- the scale form
+ * of the reference's sent_msgs / recv_msgs (EmulNet.cpp:111, :172) and of msgcount.log.  While a
+ * ledger is open every tick runs two small passes: one over the tick's receiver CSR before the
+ * tick kernels, one over the tick's send slots once they are final.  With no ledger open nothing
+ * is added to step.
+ * A ledger opened at engine tick T0 covers the sends made and the messages taken at ticks t in
+ * (T0, T], T the engine's tick at get.  x is alive at t while start[x] <= t <= crash[x] (the
+ * census's rule).  Per node, n elements each:
+ *   sent[x]       messages x put on the network: the sends that survived the drop test, counted
+ *                 at the tick they are sent; a delivered JOINREP counts for node 0
+ *   recv[r]       messages addressed to r at a tick at which r is alive, before any inbox cut (a
+ *                 JOINREP is one message)
+ *   merged[r]     of those, the ones r merges: all of them in the full view and with inbox = 0,
+ *                 else the `inbox` smallest senders (a JOINREP first); recv - merged is the inbox
+ *                 overflow at r
+ *   lost[r]       messages addressed to r at a tick at which r is not alive
+ *   entries_in[r] over r's merged messages, 1 + payload entries -- r's share of the digest's
+ *                 merges.  A GOSSIP from s carries s's gossipable members at the send tick (TFAIL
+ *                 suspects left out), a JOINREP min(intro_list, node 0's gossipable members)
+ *   peak_recv[r], peak_tick[r]  the largest recv of one tick and the first tick it occurred (-1:
+ *                 r received nothing)
+ *   state         as in the census, at T
+ * Per tick t < min(tick_cap, T + 1):
+ *   by_tick[t][6] sent, recv, merged, lost, entries and the largest recv of that tick
+ *   fanin[t][18]  the receivers alive at t by the messages k they were sent: bucket 0 holds k = 0,
+ *                 bucket b >= 1 holds 2^(b-1) <= k < 2^b, the last bucket is open-ended
+ *   watch[w][t][2]  (sent, recv) of the w-th watched node at t; the caller's array is
+ *                 [n_watch][tick_cap][2]
+ * Rows of ticks outside (T0, T] are 0.  Any out pointer may be NULL.
+ * open     watch: up to 1,024 distinct node ids in [0, n) (NULL with n_watch = 0: none);
+ *          GSP_ERR_INVALID otherwise, and while a ledger is open.
+ * get      synchronises (a pending capacity error returns GSP_ERR_CAPACITY as the other reads do).
+ * close    frees the ledger; step is back to the launches it makes without one.
+ * The result is the same for every layout and number of shards.  With a communicator open, get
+ * and close are COLLECTIVE (row shards all-reduce SUM / MAX into a staging buffer at get).
+ * ---------------------------------------------------------------------------------- */
+#define GSP_TRAFFIC_BUCKETS 18
+#define GSP_TRAFFIC_MAX_WATCH 1024
+
+typedef struct {
+    int32_t tick, n;
+    int32_t open_tick;     /* the engine's tick at open                                     */
+    int32_t ticks_counted; /* ticks stepped since open                                      */
+    int32_t n_watch;
+    int32_t reserved;
+    int64_t sent, recv, merged, lost, entries, overflow;   /* over the ticks in (T0, T]     */
+    int32_t max_fanin;     /* the largest recv of one node and tick                         */
+    int32_t max_fanin_node;/* the node that took it: first tick, then smallest id; -1: none */
+    double kernel_ms;      /* HIP events around every tick's ledger launches since open,
+                              collected at sync (0: timing off)                             */
+} gsp_traffic_info;
+
+int gsp_scale_traffic_open(gsp_scale *s, const int32_t *watch, int32_t n_watch);
+int gsp_scale_traffic_get(gsp_scale *s, uint32_t *sent, uint32_t *recv, uint32_t *merged,
+                          uint32_t *lost, uint64_t *entries_in, uint32_t *peak_recv,
+                          int32_t *peak_tick, uint8_t *state, uint64_t *by_tick, uint64_t *fanin,
+                          uint32_t *watch, int32_t tick_cap, gsp_traffic_info *info);
+int gsp_scale_traffic_close(gsp_scale *s);
+/* Writes `nodes` rows of `ticks` columns (sent[i * ticks + j], recv[i * ticks + j]) as the
+ * reference's msgcount.log (EmulNet.cpp:195-216): the rows are numbered node 1..nodes, ten pairs
+ * per line, node 67 in the reference's "special" layout.  gsp_write_msgcount prints the exact
+ * engine's counters through the same formatter. */
+int gsp_traffic_write_msgcount(const char *path, const int32_t *sent, const int32_t *recv,
+                               int32_t nodes, int32_t ticks);
+
+/* ------------------------------------------------------------------------------------
  * PARTIAL-VIEW engine (BASELINE config 5): every node keeps at most `view` member entries
  * (id, hb, ts) sorted by id; a receiver merges at most `inbox` messages per tick (1..7,
  * ascending sender; the rest are counted as overflow) -- or, with inbox = 0, every message it
@@ -746,6 +812,14 @@ int gsp_pview_detect_get(gsp_pview *s, int32_t *first_remove, int32_t *last_remo
                          uint32_t *revivals, uint32_t *evicts, uint8_t *state, uint64_t *by_tick,
                          int32_t by_tick_cap, gsp_detect_info *info);
 int gsp_pview_detect_close(gsp_pview *s);
+/* As gsp_scale_traffic_* ("Traffic ledger" above); a bounded inbox merges its `inbox` smallest
+ * senders, and with TFAIL one count pass per tick sizes the payloads while a ledger is open. */
+int gsp_pview_traffic_open(gsp_pview *s, const int32_t *watch, int32_t n_watch);
+int gsp_pview_traffic_get(gsp_pview *s, uint32_t *sent, uint32_t *recv, uint32_t *merged,
+                          uint32_t *lost, uint64_t *entries_in, uint32_t *peak_recv,
+                          int32_t *peak_tick, uint8_t *state, uint64_t *by_tick, uint64_t *fanin,
+                          uint32_t *watch, int32_t tick_cap, gsp_traffic_info *info);
+int gsp_pview_traffic_close(gsp_pview *s);
 /* Test diagnostics: the rows the tick kernels of tick t ran, summed over the shards held here
  * -- every row exactly once in every launch form, so it equals the rows held.  Needs the
  * environment variable GSP_TEST_PV_COUNT_ROWS=1 at create (else GSP_ERR_INVALID). */

@@ -124,6 +124,16 @@ class GspCensusInfo(ctypes.Structure):
 _CENSUS = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(ctypes.c_uint32), P(ctypes.c_uint32),
                           P(ctypes.c_uint32), P(ctypes.c_uint8), P(GspCensusInfo)])
 
+
+class GspAuditInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("alive", c_int32),
+                ("entries", c_int64), ("kernel_ms", ctypes.c_double)]
+
+
+_AUDIT = (ctypes.c_int, [ctypes.c_void_p, c_int32] + [P(ctypes.c_uint32)] * 4 +
+          [P(ctypes.c_uint8), P(c_uint64), P(ctypes.c_uint8), P(GspAuditInfo)])
+
+
 class GspReachInfo(ctypes.Structure):
     _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("direction", c_int32),
                 ("alive", c_int32), ("sources", c_int32), ("reached", c_int32), ("depth", c_int32),
@@ -201,6 +211,8 @@ SIGNATURES = {
     "gsp_pview_rumor_close": _RUMOR_CLOSE,
     "gsp_scale_census": _CENSUS,
     "gsp_pview_census": _CENSUS,
+    "gsp_scale_audit": _AUDIT,
+    "gsp_pview_audit": _AUDIT,
     "gsp_scale_reach": _REACH,
     "gsp_pview_reach": _REACH,
     "gsp_last_error": (ctypes.c_char_p, []),

@@ -6,7 +6,7 @@
 // only those members.  Here: the stream, the timing-event pool, the failure / join schedule,
 // the communicator, the capacity flag and its host mirror, the single-shard CSR build, the
 // JOINREP sends, the call into the row exchange (rowx_host.hpp), the host side of the census,
-// of the overlay reach, of the rumor trace, of the detection ledger and of the traffic ledger, and
+// of the view audit, of the overlay reach, of the rumor trace, of the detection ledger and of the traffic ledger, and
 // the C-ABI bodies that are the same code.
 // Tables, tick arguments, kernels launched and test knobs stay with each engine.
 #pragma once
@@ -17,6 +17,7 @@
 #include <cstring>
 #include <vector>
 
+#include "audit_kernels.hpp"
 #include "census_kernels.hpp"
 #include "common.hpp"
 #include "detect_kernels.hpp"
@@ -63,6 +64,29 @@ struct CensusBufs {
     void release() {
         for (auto *b : {&listed, &fresh, &max_hb}) b->release();
         counts.release();
+        for (hipEvent_t e : {t0, t1})
+            if (e) (void)hipEventDestroy(e);
+        t0 = t1 = nullptr;
+    }
+};
+
+// The view-audit accumulators (gsp_scale_audit / gsp_pview_audit), allocated by the first call:
+// arr holds the five n-length uint32 arrays (audit_kernels.hpp), print the fingerprints; alive /
+// fp are the per-call truth the prologue kernel writes (fp: full view only).
+struct AuditBufs {
+    DevBuf<uint32_t> arr;
+    DevBuf<unsigned long long> print;
+    DevBuf<uint8_t> alive;
+    DevBuf<uint64_t> fp;
+    std::vector<uint32_t> h32;
+    std::vector<unsigned long long> h64;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+
+    void release() {
+        arr.release();
+        print.release();
+        alive.release();
+        fp.release();
         for (hipEvent_t e : {t0, t1})
             if (e) (void)hipEventDestroy(e);
         t0 = t1 = nullptr;
@@ -196,6 +220,7 @@ struct EngineCore {
     std::vector<hipEvent_t> free_events;
     gsp_scale_perf perf{};
     CensusBufs census;
+    AuditBufs audit;
     ReachBufs reach;
     RumorBufs rumor;
     DetectBufs detect;
@@ -277,6 +302,7 @@ inline void engine_close(EngineCore &c) {
     for (hipEvent_t e : c.free_events) (void)hipEventDestroy(e);
     if (c.comm) (void)ncclCommDestroy(c.comm);
     c.census.release();
+    c.audit.release();
     c.reach.release();
     for (auto &e : c.rumor.pending) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
     c.rumor.pending.clear();
@@ -646,6 +672,76 @@ int census_run(E &s, bool packed, int32_t age_limit, uint32_t *listed,
         float ms = 0.f;
         if (s.timing) GSP_HIP(hipEventElapsedTime(&ms, c.t0, c.t1));
         *info = gsp_census_info{T, s.p.n, age_limit, alive, entries, double(ms)};
+    }
+    return GSP_OK;
+}
+
+// The view audit of the engine's current tick T (gossip.h, audit_kernels.hpp), after the engine
+// has synchronised and reported any pending capacity error.  `full`: the full view, whose kernel
+// reads the fingerprint table.  The prologue writes the call's truth (alive bitmap, fp table);
+// launch(shard) adds that shard's share -- its rows, its columns -- to the zeroed arrays; with a
+// communicator the arrays are then all-reduced on the engine's stream (SUM for the counts and the
+// wrapping print, MAX for age_max), so every rank must make the call at the same tick.  The
+// observer's own fingerprint joins print in the readback loop.
+template <class E, class Launch>
+int audit_run(E &s, bool full, int32_t age_limit, uint32_t *size, uint32_t *dead, uint32_t *suspect,
+              uint32_t *age_sum, uint8_t *age_max, uint64_t *print, uint8_t *state,
+              gsp_audit_info *info, Launch launch) {
+    const size_t n = size_t(s.p.n);
+    const int32_t T = s.tick;
+    AuditBufs &b = s.audit;
+    if (!b.t1) {                       // first call (t1 is made last: a failed attempt starts over)
+        GSP_HIP(b.arr.alloc(size_t(kAuditFields) * n));
+        GSP_HIP(b.print.alloc(n));
+        GSP_HIP(b.alive.alloc((n + 7) / 8));
+        if (full) GSP_HIP(b.fp.alloc(n));
+        if (!b.t0) GSP_HIP(hipEventCreate(&b.t0));
+        GSP_HIP(hipEventCreate(&b.t1));
+    }
+    b.h32.resize(size_t(kAuditFields) * n);
+    b.h64.resize(n);
+    GSP_HIP(hipMemsetAsync(b.arr.p, 0, size_t(kAuditFields) * n * 4, s.st));
+    GSP_HIP(hipMemsetAsync(b.print.p, 0, n * 8, s.st));
+    if (s.timing) GSP_HIP(hipEventRecord(b.t0, s.st));
+    AuditTruthArgs tr{};
+    tr.n = s.p.n;
+    tr.tick = T;
+    tr.fail_tick = s.local[0].fail_tick.p;
+    tr.start_tick = s.joins ? s.local[0].start_tick.p : nullptr;
+    tr.alive = b.alive.p;
+    tr.fp = full ? b.fp.p : nullptr;
+    GSP_HIP(launch_audit_truth(tr, s.st));
+    for (auto &sh : s.local)
+        if (int rc = launch(sh)) return rc;
+    if (s.timing) GSP_HIP(hipEventRecord(b.t1, s.st));
+    if (s.comm) {
+        uint32_t *mx = b.arr.p + size_t(kAudAgeMax) * n;
+        GSP_NCCL(ncclAllReduce(b.arr.p, b.arr.p, size_t(kAudAgeMax) * n, ncclUint32, ncclSum, s.comm, s.st));
+        GSP_NCCL(ncclAllReduce(mx, mx, n, ncclUint32, ncclMax, s.comm, s.st));
+        GSP_NCCL(ncclAllReduce(b.print.p, b.print.p, n, ncclUint64, ncclSum, s.comm, s.st));
+    }
+    GSP_HIP(hipMemcpyAsync(b.h32.data(), b.arr.p, size_t(kAuditFields) * n * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipMemcpyAsync(b.h64.data(), b.print.p, n * 8, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    const uint32_t *h = b.h32.data();
+    int64_t entries = 0;
+    int32_t alive = 0;
+    for (size_t r = 0; r < n; ++r) {
+        const uint8_t st = T < s.h_start[r] ? 0 : T <= s.h_fail[r] ? 1 : 2;
+        entries += h[size_t(kAudSize) * n + r];
+        alive += st == 1;
+        if (size) size[r] = h[size_t(kAudSize) * n + r];
+        if (dead) dead[r] = h[size_t(kAudDead) * n + r];
+        if (suspect) suspect[r] = h[size_t(kAudSuspect) * n + r];
+        if (age_sum) age_sum[r] = h[size_t(kAudAgeSum) * n + r];
+        if (age_max) age_max[r] = uint8_t(h[size_t(kAudAgeMax) * n + r]);
+        if (print) print[r] = st == 1 ? uint64_t(b.h64[r]) + audit_fp(uint32_t(r)) : 0;
+        if (state) state[r] = st;
+    }
+    if (info) {
+        float ms = 0.f;
+        if (s.timing) GSP_HIP(hipEventElapsedTime(&ms, b.t0, b.t1));
+        *info = gsp_audit_info{T, s.p.n, age_limit, alive, entries, double(ms)};
     }
     return GSP_OK;
 }

@@ -739,6 +739,37 @@ int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t
     });
 }
 
+// View audit of the current tick (engine_host.hpp audit_run): every local shard adds its rows x
+// columns -- the fused table, a column tile from col0, a row shard from row0.
+int gsp_scale_audit(gsp_scale *s, int32_t age_limit, uint32_t *size, uint32_t *dead,
+                    uint32_t *suspect, uint32_t *age_sum, uint8_t *age_max, uint64_t *print,
+                    uint8_t *state, gsp_audit_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_audit: NULL");
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
+                "gsp_scale_audit: age_limit=%d outside [1,32]", age_limit);
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::audit_run(*s, true, age_limit, size, dead, suspect, age_sum, age_max, print, state, info,
+                          [&](Shard &sh) -> int {
+        gsp::AuditScaleArgs a{};
+        a.table = sh.table[s->tick & 1].p;
+        a.stride = s->stride;
+        a.n = s->p.n;
+        a.col0 = sh.col0;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        a.tick = s->tick;
+        a.age_limit = age_limit;
+        a.fail_tick = sh.fail_tick.p;
+        a.start_tick = s->joins ? sh.start_tick.p : nullptr;
+        a.alive = s->audit.alive.p;
+        a.fp = s->audit.fp.p;
+        a.arr = s->audit.arr.p;
+        a.print = s->audit.print.p;
+        GSP_HIP(gsp::launch_audit_scale(a, s->st));
+        return GSP_OK;
+    });
+}
+
 // Overlay reach of the current tick (engine_host.hpp reach_run): per level every local shard
 // runs its rows x columns -- the fused table, a column tile from col0, a row shard from row0.
 int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const int32_t *sources,

@@ -116,6 +116,15 @@ class PviewEngine:
             age_limit = census.default_age_limit(self.params)
         return census.run(lib().gsp_pview_census, self._h, self.n, age_limit, "gsp_pview_census")
 
+    def audit(self, age_limit=None):
+        """The view audit of the current tick (audit.Audit): per alive observer what its view
+        holds and its fingerprint; age_limit (1..32) bounds `suspect`, default as for census().
+        Collective across the ranks of a job."""
+        from . import audit, census
+        if age_limit is None:
+            age_limit = census.default_age_limit(self.params)
+        return audit.run(lib().gsp_pview_audit, self._h, self.n, age_limit, "gsp_pview_audit")
+
     def reach(self, sources=0, direction="from", age_limit=None):
         """BFS hop counts over the membership graph of the current tick (reach.Reach), from
         (direction "from") or towards ("to") `sources`, an id or a sequence of ids; an edge is

@@ -504,6 +504,46 @@ int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t
                      uint32_t *max_hb, uint8_t *state, gsp_census_info *info);
 
 /* ------------------------------------------------------------------------------------
+ * View audit: the row-wise twin of the census -- what is wrong with each observer's view, and
+ * do the live nodes agree -- asked of the tables in HBM at the engine's current tick T (every
+ * tick submitted so far; valid at T = 0).  One streaming pass per call, nothing added to create
+ * or step.  A row r is alive at T iff start[r] <= T <= crash[r]; only alive rows are read (a
+ * crashed row's buffer is stale) and a row that is not alive gets 0 in every array.  For an
+ * entry a view stores, age = (T - ts) mod 32.  For every alive observer r, over the entries its
+ * view stores, buffers of n elements each, any of them NULL:
+ *   size[r]     entries stored
+ *   dead[r]     entries whose member is not alive at T (r's completeness debt)
+ *   suspect[r]  entries of alive members with age >= age_limit (1..32; 32: always 0)
+ *   age_sum[r]  sum of the age over the entries of alive members
+ *   age_max[r]  the largest such age: tremove - 1 - age_max[r] is r's margin before it removes a
+ *               live member
+ *   print[r]    the fingerprint of view(r) + {r}: the sum mod 2^64 of fp(x) over those ids, fp
+ *               the splitmix64 finaliser (z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ *               0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; fp = z ^ z >> 31).
+ *               No view stores its owner, so fp(r) is added: two nodes with the same knowledge
+ *               have the same print.  A 64-bit sum can collide: equal prints are a fingerprint
+ *               of agreement, not a proof.
+ *   state[r]    0 not started yet, 1 alive at T, 2 crashed, as in the census
+ * The arrays are the same for every layout and number of shards.  With a communicator
+ * (gsp_*_create_rank*) the call is COLLECTIVE, like the census: each rank audits the rows and
+ * columns it holds and the arrays are all-reduced on the engine's stream (SUM; MAX for age_max),
+ * so every rank must make the call at the same tick, and every rank gets the whole result.  A
+ * pending capacity error returns GSP_ERR_CAPACITY as the other reads do.  The accumulators (28 B
+ * per node, and the call's truth: 1 bit per node, full view 8 B more) are allocated by the first
+ * call and freed at destroy.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t tick, n, age_limit;
+    int32_t alive;        /* nodes with state 1                                  */
+    int64_t entries;      /* sum of size[]                                       */
+    double kernel_ms;     /* HIP events around the audit kernels (0: timing off) */
+} gsp_audit_info;
+
+int gsp_scale_audit(gsp_scale *s, int32_t age_limit, uint32_t *size, uint32_t *dead,
+                    uint32_t *suspect, uint32_t *age_sum, uint8_t *age_max, uint64_t *print,
+                    uint8_t *state, gsp_audit_info *info);
+
+/* ------------------------------------------------------------------------------------
  * Overlay reach: hop counts over the membership graph of the engine's current tick T (every
  * tick submitted so far; valid at T = 0), by a level-synchronous BFS on the tables in HBM.
  * Nothing is added to create or step.  Vertices are the nodes alive at T (the census's rule:
@@ -794,6 +834,10 @@ int gsp_pview_drain_stats(gsp_pview *s, int32_t classes, int64_t *rows, int64_t 
 /* As gsp_scale_census ("Membership census" above), over the views. */
 int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
                      uint32_t *max_hb, uint8_t *state, gsp_census_info *info);
+/* As gsp_scale_audit ("View audit" above), over the views. */
+int gsp_pview_audit(gsp_pview *s, int32_t age_limit, uint32_t *size, uint32_t *dead,
+                    uint32_t *suspect, uint32_t *age_sum, uint8_t *age_max, uint64_t *print,
+                    uint8_t *state, gsp_audit_info *info);
 /* As gsp_scale_reach ("Overlay reach" above): a view is its row's out-edge list. */
 int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);

@@ -186,35 +186,16 @@ _TRAFFIC_GET = (ctypes.c_int, [ctypes.c_void_p] + [P(ctypes.c_uint32)] * 4 + [P(
                                c_int32, P(GspTrafficInfo)])
 _TRAFFIC_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
 
+_PROBES = {                     # the probe entry points both scale engines export (probes.py)
+    "census": _CENSUS, "audit": _AUDIT, "reach": _REACH,
+    "rumor_open": _RUMOR_OPEN, "rumor_seed": _RUMOR_SEED, "rumor_get": _RUMOR_GET, "rumor_close": _RUMOR_CLOSE,
+    "detect_open": _DETECT_OPEN, "detect_get": _DETECT_GET, "detect_close": _DETECT_OPEN,
+    "traffic_open": _TRAFFIC_OPEN, "traffic_get": _TRAFFIC_GET, "traffic_close": _TRAFFIC_CLOSE,
+}
 # name -> (restype, argtypes); every name here must be exported (tests check it)
 SIGNATURES = {
-    "gsp_scale_traffic_open": _TRAFFIC_OPEN,
-    "gsp_scale_traffic_get": _TRAFFIC_GET,
-    "gsp_scale_traffic_close": _TRAFFIC_CLOSE,
-    "gsp_pview_traffic_open": _TRAFFIC_OPEN,
-    "gsp_pview_traffic_get": _TRAFFIC_GET,
-    "gsp_pview_traffic_close": _TRAFFIC_CLOSE,
+    **{"%s_%s" % (abi, name): sig for abi in ("gsp_scale", "gsp_pview") for name, sig in _PROBES.items()},
     "gsp_traffic_write_msgcount": (ctypes.c_int, [ctypes.c_char_p, P(c_int32), P(c_int32), c_int32, c_int32]),
-    "gsp_scale_detect_open": _DETECT_OPEN,
-    "gsp_scale_detect_get": _DETECT_GET,
-    "gsp_scale_detect_close": _DETECT_OPEN,
-    "gsp_pview_detect_open": _DETECT_OPEN,
-    "gsp_pview_detect_get": _DETECT_GET,
-    "gsp_pview_detect_close": _DETECT_OPEN,
-    "gsp_scale_rumor_open": _RUMOR_OPEN,
-    "gsp_scale_rumor_seed": _RUMOR_SEED,
-    "gsp_scale_rumor_get": _RUMOR_GET,
-    "gsp_scale_rumor_close": _RUMOR_CLOSE,
-    "gsp_pview_rumor_open": _RUMOR_OPEN,
-    "gsp_pview_rumor_seed": _RUMOR_SEED,
-    "gsp_pview_rumor_get": _RUMOR_GET,
-    "gsp_pview_rumor_close": _RUMOR_CLOSE,
-    "gsp_scale_census": _CENSUS,
-    "gsp_pview_census": _CENSUS,
-    "gsp_scale_audit": _AUDIT,
-    "gsp_pview_audit": _AUDIT,
-    "gsp_scale_reach": _REACH,
-    "gsp_pview_reach": _REACH,
     "gsp_last_error": (ctypes.c_char_p, []),
     "gsp_abi_version": (ctypes.c_int, []),
     "gsp_device_count": (ctypes.c_int, []),

@@ -84,4 +84,10 @@ struct DevBuf {
     }
 };
 
+// release() of every argument, in order: buffers of different element types, and structs of them
+template <class... B>
+void release_all(B &...b) {
+    (b.release(), ...);
+}
+
 }  // namespace gsp

@@ -17,8 +17,9 @@
 // The skeleton shared with the full-view engine is engine_host.hpp: stream, event pool and
 // timing, failure / join schedule, communicator, capacity flag, common shard buffers, the
 // single-shard CSR build, JOINREP sends, the call into the row exchange and the C-ABI bodies
-// that are the same code.  Here: the view tables, the receipt / split / drain / nowait state,
-// the tick arguments and the drain-class accounting.
+// that are the same code; on top of it probes_host.hpp, the host side of the six probes.  Here:
+// the view tables, the receipt / split / drain / nowait state, the tick arguments and the
+// drain-class accounting.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -29,8 +30,8 @@
 #include <memory>
 #include <vector>
 
-#include "engine_host.hpp"
 #include "philox.hpp"
+#include "probes_host.hpp"
 #include "pview_kernels.hpp"
 
 namespace {
@@ -58,7 +59,7 @@ struct PvShard : gsp::ShardCore {
 
 }  // namespace
 
-struct gsp_pview : gsp::EngineCore {    // shards: row shards; rowmode: G > 1 or any communicator
+struct gsp_pview : gsp::ProbeCore {    // shards: row shards; rowmode: G > 1 or any communicator
     gsp_pview_params p{};
     int32_t split = 1;           // GSP_TEST_PV_SPLIT=0: every row in the one 256-lane kernel; else
                                  // rows bucketed by k into four kernels (pview_kernels.hip)
@@ -253,7 +254,7 @@ gsp::JoinForm join_form(const gsp_pview *s) {
 
 // sync, after the stream: the timed ticks, the drain classes' times and sizes, the capacity flag
 int pview_collect(gsp_pview *s) {
-    if (int rc = gsp::collect_timing(*s)) return rc;
+    if (int rc = gsp::collect_timing(*s)) return rc;       // the probes' spans too (probes_host.hpp)
     for (auto &de : s->dpending) {
         GSP_HIP(hipEventSynchronize(de[gsp::kDrainClasses]));
         for (int c = 0; c < gsp::kDrainClasses; ++c) {
@@ -455,7 +456,7 @@ int gsp_pview_destroy(gsp_pview *s) {
     if (s->drain_fork) (void)hipEventDestroy(s->drain_fork);
     if (s->drain_join) (void)hipEventDestroy(s->drain_join);
     if (s->drain_st) (void)hipStreamDestroy(s->drain_st);
-    gsp::engine_close(*s);
+    gsp::engine_close(*s);     // the probes' state, then the core (probes_host.hpp)
     delete s;
     return GSP_OK;
 }
@@ -636,17 +637,19 @@ int gsp_pview_drain_stats(gsp_pview *s, int32_t classes, int64_t *rows, int64_t 
     return GSP_OK;
 }
 
-// Census of the current tick (engine_host.hpp census_run): every local shard adds its rows.
+// The probes (probes_host.hpp).  A snapshot or a get syncs the engine and runs the shared body;
+// open, seed and close are the shared body alone.
+
+// Census of the current tick (census_run): every local shard adds its rows.
 // GSP_TEST_PV_CENSUS=0|1 (tests, A/B) selects the plain / the LDS-privatised kernel form.
 int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
                      uint32_t *max_hb, uint8_t *state, gsp_census_info *info) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_census: NULL");
-    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
-                "gsp_pview_census: age_limit=%d outside [1,32]", age_limit);
     if (int rc = gsp_pview_sync(s)) return rc;
     bool lds = gsp::kCensusPviewLds;
     if (const char *f = std::getenv("GSP_TEST_PV_CENSUS")) lds = std::atoi(f) != 0;
-    return gsp::census_run(*s, true, age_limit, listed, fresh, max_hb, state, info, [&](PvShard &sh) -> int {
+    return gsp::census_run(*s, "gsp_pview_census", true, age_limit, listed, fresh, max_hb, state, info,
+                           [&](PvShard &sh) -> int {
         gsp::CensusPviewArgs a{};
         a.table = sh.table[s->tick & 1].p;
         a.len = sh.len[s->tick & 1].p;
@@ -665,16 +668,14 @@ int gsp_pview_census(gsp_pview *s, int32_t age_limit, uint32_t *listed, uint32_t
     });
 }
 
-// View audit of the current tick (engine_host.hpp audit_run): every local shard stores its rows.
+// View audit of the current tick (audit_run): every local shard stores its rows.
 int gsp_pview_audit(gsp_pview *s, int32_t age_limit, uint32_t *size, uint32_t *dead,
                     uint32_t *suspect, uint32_t *age_sum, uint8_t *age_max, uint64_t *print,
                     uint8_t *state, gsp_audit_info *info) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_audit: NULL");
-    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
-                "gsp_pview_audit: age_limit=%d outside [1,32]", age_limit);
     if (int rc = gsp_pview_sync(s)) return rc;
-    return gsp::audit_run(*s, false, age_limit, size, dead, suspect, age_sum, age_max, print, state, info,
-                          [&](PvShard &sh) -> int {
+    return gsp::audit_run(*s, "gsp_pview_audit", false, age_limit, size, dead, suspect, age_sum, age_max,
+                          print, state, info, [&](PvShard &sh) -> int {
         gsp::AuditPviewArgs a{};
         a.table = sh.table[s->tick & 1].p;
         a.len = sh.len[s->tick & 1].p;
@@ -694,8 +695,7 @@ int gsp_pview_audit(gsp_pview *s, int32_t age_limit, uint32_t *size, uint32_t *d
     });
 }
 
-// Overlay reach of the current tick (engine_host.hpp reach_run): per level every local shard
-// runs its rows.
+// Overlay reach of the current tick (reach_run): per level every local shard runs its rows.
 int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_reach: NULL");
@@ -714,18 +714,14 @@ int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const in
     });
 }
 
-// Rumor trace (engine_host.hpp rumor_*): a bounded inbox hears the senders of its receipt
-// record, drain all every entry of the segment.
+// Rumor trace (rumor_*): a bounded inbox hears the senders of its receipt record, drain all every
+// entry of the segment.
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_open: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::rumor_open(*s, "gsp_pview_rumor_open", rumors);
+    return gsp::rumor_open(s, "gsp_pview_rumor_open", rumors);
 }
 
 int gsp_pview_rumor_seed(gsp_pview *s, int32_t rumor, const int32_t *sources, int32_t n_sources) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_seed: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::rumor_seed(*s, "gsp_pview_rumor_seed", rumor, sources, n_sources);
+    return gsp::rumor_seed(s, "gsp_pview_rumor_seed", rumor, sources, n_sources);
 }
 
 int gsp_pview_rumor_get(gsp_pview *s, int32_t rumor, int32_t *heard, uint8_t *state, int32_t *known,
@@ -736,16 +732,12 @@ int gsp_pview_rumor_get(gsp_pview *s, int32_t rumor, int32_t *heard, uint8_t *st
 }
 
 int gsp_pview_rumor_close(gsp_pview *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_rumor_close: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::rumor_close(*s, "gsp_pview_rumor_close");
+    return gsp::probe_close(s, "gsp_pview_rumor_close", &gsp::ProbeCore::rumor, "trace");
 }
 
-// Detection ledger (engine_host.hpp detect_*): join, remove and evict records.
+// Detection ledger (detect_*): join, remove and evict records.
 int gsp_pview_detect_open(gsp_pview *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_detect_open: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::detect_open(*s, "gsp_pview_detect_open");
+    return gsp::detect_open(s, "gsp_pview_detect_open");
 }
 
 int gsp_pview_detect_get(gsp_pview *s, int32_t *first_remove, int32_t *last_remove, uint32_t *removers,
@@ -759,17 +751,14 @@ int gsp_pview_detect_get(gsp_pview *s, int32_t *first_remove, int32_t *last_remo
 }
 
 int gsp_pview_detect_close(gsp_pview *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_detect_close: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::detect_close(*s, "gsp_pview_detect_close");
+    return gsp::probe_close(s, "gsp_pview_detect_close", &gsp::ProbeCore::detect, "ledger");
 }
 
-// Traffic ledger (engine_host.hpp traffic_*): the ledger keeps its own psize[n] when the sizes
-// are not one shard's plain row lengths (TFAIL, or row shards).
+// Traffic ledger (traffic_*): the ledger keeps its own psize[n] when the sizes are not one shard's
+// plain row lengths (TFAIL, or row shards).
 int gsp_pview_traffic_open(gsp_pview *s, const int32_t *watch, int32_t n_watch) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_traffic_open: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::traffic_open(*s, "gsp_pview_traffic_open", watch, n_watch, s->p.tfail > 0 || s->rowmode);
+    const bool own_sizes = s && (s->p.tfail > 0 || s->rowmode);     // NULL: the body reports it
+    return gsp::traffic_open(s, "gsp_pview_traffic_open", watch, n_watch, own_sizes);
 }
 
 int gsp_pview_traffic_get(gsp_pview *s, uint32_t *sent, uint32_t *recv, uint32_t *merged, uint32_t *lost,
@@ -783,9 +772,7 @@ int gsp_pview_traffic_get(gsp_pview *s, uint32_t *sent, uint32_t *recv, uint32_t
 }
 
 int gsp_pview_traffic_close(gsp_pview *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_traffic_close: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::traffic_close(*s, "gsp_pview_traffic_close");
+    return gsp::probe_close(s, "gsp_pview_traffic_close", &gsp::ProbeCore::traffic, "ledger");
 }
 
 int gsp_pview_perf_get(gsp_pview *s, gsp_scale_perf *out) {

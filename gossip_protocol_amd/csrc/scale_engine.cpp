@@ -15,8 +15,9 @@
 // The skeleton shared with the partial-view engine is engine_host.hpp: stream, event pool and
 // timing, failure / join schedule, communicator, capacity flag, common shard buffers, the
 // single-shard CSR build, JOINREP sends, the call into the row exchange and the C-ABI bodies
-// that are the same code.  Here: the tables and column / slice state, the tick arguments, the
-// count / pick exchanges, the sweep and the long-row table.
+// that are the same code; on top of it probes_host.hpp, the host side of the six probes.  Here:
+// the tables and column / slice state, the tick arguments, the count / pick exchanges, the sweep
+// and the long-row table.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -26,8 +27,8 @@
 #include <memory>
 #include <vector>
 
-#include "engine_host.hpp"
 #include "philox.hpp"
+#include "probes_host.hpp"
 
 namespace {
 
@@ -54,7 +55,7 @@ struct Shard : gsp::ShardCore {
 
 }  // namespace
 
-struct gsp_scale : gsp::EngineCore {
+struct gsp_scale : gsp::ProbeCore {
     gsp_scale_params p{};
     bool sliced = false;       // column layout (G > 1)
     bool shared = false;       // column layout, every shard in this process on one device (an
@@ -508,7 +509,7 @@ int gsp_scale_destroy(gsp_scale *s) {
     if (s->st) (void)hipStreamSynchronize(s->st);
     for (Shard &sh : s->local) sh.release();
     s->long_tpl.release();
-    gsp::engine_close(*s);
+    gsp::engine_close(*s);     // the probes' state, then the core (probes_host.hpp)
     delete s;
     return GSP_OK;
 }
@@ -589,7 +590,7 @@ int gsp_scale_sync(gsp_scale *s) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_sync: NULL");
     GSP_HIP(hipSetDevice(s->device));
     GSP_HIP(hipStreamSynchronize(s->st));
-    if (int rc = gsp::collect_timing(*s)) return rc;
+    if (int rc = gsp::collect_timing(*s)) return rc;       // the probes' spans too (probes_host.hpp)
     return gsp::check_err(s, 0);       // 0: the full view sets no drain-all bit
 }
 
@@ -711,15 +712,17 @@ int gsp_scale_drain_events(gsp_scale *s, uint64_t *buf, int64_t cap, int64_t *n,
     return gsp::drain_events(*s, buf, cap, n, lost);
 }
 
-// Census of the current tick (engine_host.hpp census_run): every local shard adds its rows x
-// columns -- the fused table, a column tile from col0, a row shard from row0.
+// The probes (probes_host.hpp).  A snapshot or a get syncs the engine and runs the shared body;
+// open, seed and close are the shared body alone.
+
+// Census of the current tick (census_run): every local shard adds its rows x columns -- the fused
+// table, a column tile from col0, a row shard from row0.
 int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t *fresh,
                      uint32_t *max_hb, uint8_t *state, gsp_census_info *info) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_census: NULL");
-    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
-                "gsp_scale_census: age_limit=%d outside [1,32]", age_limit);
     if (int rc = gsp_scale_sync(s)) return rc;
-    return gsp::census_run(*s, false, age_limit, listed, fresh, max_hb, state, info, [&](Shard &sh) -> int {
+    return gsp::census_run(*s, "gsp_scale_census", false, age_limit, listed, fresh, max_hb, state, info,
+                           [&](Shard &sh) -> int {
         gsp::CensusScaleArgs a{};
         a.table = sh.table[s->tick & 1].p;
         a.stride = s->stride;
@@ -739,17 +742,15 @@ int gsp_scale_census(gsp_scale *s, int32_t age_limit, uint32_t *listed, uint32_t
     });
 }
 
-// View audit of the current tick (engine_host.hpp audit_run): every local shard adds its rows x
-// columns -- the fused table, a column tile from col0, a row shard from row0.
+// View audit of the current tick (audit_run): every local shard adds its rows x columns -- the
+// fused table, a column tile from col0, a row shard from row0.
 int gsp_scale_audit(gsp_scale *s, int32_t age_limit, uint32_t *size, uint32_t *dead,
                     uint32_t *suspect, uint32_t *age_sum, uint8_t *age_max, uint64_t *print,
                     uint8_t *state, gsp_audit_info *info) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_audit: NULL");
-    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID,
-                "gsp_scale_audit: age_limit=%d outside [1,32]", age_limit);
     if (int rc = gsp_scale_sync(s)) return rc;
-    return gsp::audit_run(*s, true, age_limit, size, dead, suspect, age_sum, age_max, print, state, info,
-                          [&](Shard &sh) -> int {
+    return gsp::audit_run(*s, "gsp_scale_audit", true, age_limit, size, dead, suspect, age_sum, age_max,
+                          print, state, info, [&](Shard &sh) -> int {
         gsp::AuditScaleArgs a{};
         a.table = sh.table[s->tick & 1].p;
         a.stride = s->stride;
@@ -770,8 +771,8 @@ int gsp_scale_audit(gsp_scale *s, int32_t age_limit, uint32_t *size, uint32_t *d
     });
 }
 
-// Overlay reach of the current tick (engine_host.hpp reach_run): per level every local shard
-// runs its rows x columns -- the fused table, a column tile from col0, a row shard from row0.
+// Overlay reach of the current tick (reach_run): per level every local shard runs its rows x
+// columns -- the fused table, a column tile from col0, a row shard from row0.
 int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const int32_t *sources,
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_reach: NULL");
@@ -790,17 +791,13 @@ int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const in
     });
 }
 
-// Rumor trace (engine_host.hpp rumor_*): every entry of a receiver's segment is heard.
+// Rumor trace (rumor_*): every entry of a receiver's segment is heard.
 int gsp_scale_rumor_open(gsp_scale *s, int32_t rumors) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_open: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::rumor_open(*s, "gsp_scale_rumor_open", rumors);
+    return gsp::rumor_open(s, "gsp_scale_rumor_open", rumors);
 }
 
 int gsp_scale_rumor_seed(gsp_scale *s, int32_t rumor, const int32_t *sources, int32_t n_sources) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_seed: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::rumor_seed(*s, "gsp_scale_rumor_seed", rumor, sources, n_sources);
+    return gsp::rumor_seed(s, "gsp_scale_rumor_seed", rumor, sources, n_sources);
 }
 
 int gsp_scale_rumor_get(gsp_scale *s, int32_t rumor, int32_t *heard, uint8_t *state, int32_t *known,
@@ -811,16 +808,12 @@ int gsp_scale_rumor_get(gsp_scale *s, int32_t rumor, int32_t *heard, uint8_t *st
 }
 
 int gsp_scale_rumor_close(gsp_scale *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_rumor_close: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::rumor_close(*s, "gsp_scale_rumor_close");
+    return gsp::probe_close(s, "gsp_scale_rumor_close", &gsp::ProbeCore::rumor, "trace");
 }
 
-// Detection ledger (engine_host.hpp detect_*): every local shard's ring folds into one ledger.
+// Detection ledger (detect_*): every local shard's ring folds into one ledger.
 int gsp_scale_detect_open(gsp_scale *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_detect_open: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::detect_open(*s, "gsp_scale_detect_open");
+    return gsp::detect_open(s, "gsp_scale_detect_open");
 }
 
 int gsp_scale_detect_get(gsp_scale *s, int32_t *first_remove, int32_t *last_remove, uint32_t *removers,
@@ -834,16 +827,12 @@ int gsp_scale_detect_get(gsp_scale *s, int32_t *first_remove, int32_t *last_remo
 }
 
 int gsp_scale_detect_close(gsp_scale *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_detect_close: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::detect_close(*s, "gsp_scale_detect_close");
+    return gsp::probe_close(s, "gsp_scale_detect_close", &gsp::ProbeCore::detect, "ledger");
 }
 
-// Traffic ledger (engine_host.hpp traffic_*): a GOSSIP carries its sender's member count.
+// Traffic ledger (traffic_*): a GOSSIP carries its sender's member count.
 int gsp_scale_traffic_open(gsp_scale *s, const int32_t *watch, int32_t n_watch) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_traffic_open: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::traffic_open(*s, "gsp_scale_traffic_open", watch, n_watch, false);
+    return gsp::traffic_open(s, "gsp_scale_traffic_open", watch, n_watch, false);
 }
 
 int gsp_scale_traffic_get(gsp_scale *s, uint32_t *sent, uint32_t *recv, uint32_t *merged, uint32_t *lost,
@@ -857,9 +846,7 @@ int gsp_scale_traffic_get(gsp_scale *s, uint32_t *sent, uint32_t *recv, uint32_t
 }
 
 int gsp_scale_traffic_close(gsp_scale *s) {
-    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_traffic_close: NULL");
-    GSP_HIP(hipSetDevice(s->device));
-    return gsp::traffic_close(*s, "gsp_scale_traffic_close");
+    return gsp::probe_close(s, "gsp_scale_traffic_close", &gsp::ProbeCore::traffic, "ledger");
 }
 
 int gsp_scale_hip_stream(gsp_scale *s, void **stream) {

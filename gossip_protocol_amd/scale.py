@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
+from .probes import ProbeMethods
 
 FAIL_NONE, FAIL_RANDOM, FAIL_BLOCK, FAIL_SINGLE, FAIL_HALF = 0, 1, 2, 3, 4
 make_policy = _lib.make_policy
@@ -36,8 +37,8 @@ def nccl_unique_id():
     return buf.raw
 
 
-class ScaleEngine:
-    """One scale engine.
+class ScaleEngine(ProbeMethods):
+    """One scale engine (its probes -- census() ... traffic_close() -- are probes.ProbeMethods).
 
     group=G (> 1): G shards inside this process on `device` (exchange by device copies).
     rank/world/nccl_id: this process holds shard `rank` of `world` (exchange over RCCL).
@@ -50,6 +51,8 @@ class ScaleEngine:
     swim = s > 0: SWIM ping/ack probing, one probe target per node per tick over 1 direct + s - 1
     indirect paths (answered: ts refreshed; unanswered: removed); every layout.
     """
+
+    _abi = "gsp_scale"
 
     def __init__(self, n, fanout=3, drop_pct=0, tremove=20, h0=1, fail_mode=FAIL_NONE,
                  fail_tick=10, fail_ppm=0, seed=0x5EED, max_ticks=256, device=0, group=1,
@@ -151,89 +154,6 @@ class ScaleEngine:
 
     def set_cache_policy(self, policy):
         check(lib().gsp_scale_set_cache_policy(self._h, int(policy)), "gsp_scale_set_cache_policy")
-
-    def census(self, age_limit=None):
-        """The membership census of the current tick (census.Census); age_limit (1..32) bounds
-        `fresh`, default tfail if set, else tremove.  Collective across the ranks of a job."""
-        from . import census
-        if age_limit is None:
-            age_limit = census.default_age_limit(self.params)
-        return census.run(lib().gsp_scale_census, self._h, self.n, age_limit, "gsp_scale_census")
-
-    def audit(self, age_limit=None):
-        """The view audit of the current tick (audit.Audit): per alive observer what its view
-        holds and its fingerprint; age_limit (1..32) bounds `suspect`, default as for census().
-        Collective across the ranks of a job."""
-        from . import audit, census
-        if age_limit is None:
-            age_limit = census.default_age_limit(self.params)
-        return audit.run(lib().gsp_scale_audit, self._h, self.n, age_limit, "gsp_scale_audit")
-
-    def reach(self, sources=0, direction="from", age_limit=None):
-        """BFS hop counts over the membership graph of the current tick (reach.Reach), from
-        (direction "from") or towards ("to") `sources`, an id or a sequence of ids; an edge is
-        an entry younger than age_limit (1..32), default as for census().  Collective across
-        the ranks of a job."""
-        from . import census, reach
-        if age_limit is None:
-            age_limit = census.default_age_limit(self.params)
-        return reach.run(lib().gsp_scale_reach, self._h, self.n, sources, direction, age_limit,
-                         "gsp_scale_reach")
-
-    def rumor_open(self, rumors=32):
-        """Open a rumor trace of `rumors` (1..32) independent rumors (rumor.py): from now on
-        every tick also moves them one hop over the messages delivered.  Collective."""
-        from . import rumor
-        rumor.open_trace(lib().gsp_scale_rumor_open, self._h, rumors, "gsp_scale_rumor_open")
-
-    def rumor_seed(self, rumor, sources):
-        """Give rumor `rumor` to `sources` (an id or a sequence) at the current tick; sources
-        that are not alive are ignored.  Collective."""
-        from . import rumor as _r
-        _r.seed(lib().gsp_scale_rumor_seed, self._h, rumor, sources, "gsp_scale_rumor_seed")
-
-    def rumor(self, rumor=0):
-        """rumor.Rumor of one rumor at the current tick.  Collective."""
-        from . import rumor as _r
-        return _r.get(lib().gsp_scale_rumor_get, self._h, self.n, self.params.max_ticks, rumor,
-                      "gsp_scale_rumor_get")
-
-    def rumor_close(self):
-        """Free the trace; step is back to the launches it makes without one.  Collective."""
-        check(lib().gsp_scale_rumor_close(self._h), "gsp_scale_rumor_close")
-
-    def detect_open(self):
-        """Open the detection ledger (detect.py; needs events with removes recorded): what the
-        ring holds is folded now, and from now on every tick ends with one fold of its event
-        records per member on the device, which empties the ring."""
-        check(lib().gsp_scale_detect_open(self._h), "gsp_scale_detect_open")
-
-    def detect(self):
-        """detect.Detect of the open ledger at the current tick.  Collective."""
-        from . import detect
-        return detect.get(lib().gsp_scale_detect_get, self._h, self.params, "gsp_scale_detect_get")
-
-    def detect_close(self):
-        """Free the ledger; the ring is left empty and fills and drains as before.  Collective."""
-        check(lib().gsp_scale_detect_close(self._h), "gsp_scale_detect_close")
-
-    def traffic_open(self, watch=None):
-        """Open the traffic ledger (traffic.py): from now on every tick counts, on the device,
-        what each node sends, is sent, merges and loses to dead receivers.  watch: up to 1,024
-        distinct node ids whose (sent, recv) are kept for every tick."""
-        from . import traffic
-        self._traffic_watch = traffic.open_(lib().gsp_scale_traffic_open, self._h, watch,
-                                            "gsp_scale_traffic_open")
-
-    def traffic(self):
-        """traffic.Traffic of the open ledger at the current tick.  Collective."""
-        from . import traffic
-        return traffic.get(lib().gsp_scale_traffic_get, self._h, self.params,
-                           getattr(self, "_traffic_watch", ()), "gsp_scale_traffic_get")
-
-    def traffic_close(self):
-        """Free the ledger; step is back to the launches it makes without one.  Collective."""
-        check(lib().gsp_scale_traffic_close(self._h), "gsp_scale_traffic_close")
 
     def drain_events(self):
         """(records, lost) since the last drain (events=True); see _lib.split_events."""

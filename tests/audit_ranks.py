@@ -16,7 +16,6 @@ age_max), so EVERY rank's audit at ticks 0, 12 and 13 must equal the one numpy m
 oracle's rows.  torch.distributed (gloo) carries only the RCCL id and the verdicts.  Rank 0
 prints one JSON line; exit status 0 means parity.
 """
-import json
 import os
 import sys
 
@@ -29,14 +28,10 @@ TICKS, AT, LIMITS = 13, (0, 12, 13), (3, 9)
 
 
 def run(case):
-    import torch.distributed as dist
-    from gossip_protocol_amd.dist import broadcast_bytes
-    from gossip_protocol_amd.scale import ScaleEngine, nccl_unique_id
+    from gossip_protocol_amd.scale import ScaleEngine
+    from tests import ranks_common
     from tests import audit_oracle as ao
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = int(os.environ.get("LOCAL_RANK", "0"))
-    uid = broadcast_bytes(nccl_unique_id() if rank == 0 else None)
+    dist, rank, world, dev, uid = ranks_common.start()
     if case == "pview_rows":
         from gossip_protocol_amd.pview import PviewEngine
         w, ref = ao.PVIEW["A"], ao.pview_reference("A", TICKS, AT)
@@ -60,12 +55,7 @@ def run(case):
             if got.tick != t or got.info["entries"] != int(want["size"].sum(dtype=np.int64)):
                 bad.append(("info", t, lim, got.info))
     eng.close()
-    res = [None] * world
-    dist.all_gather_object(res, {"rank": rank, "bad": [str(b)[:300] for b in bad]})
-    if rank == 0:
-        print(json.dumps({"case": case, "world": world, "ranks": res}), flush=True)
-    dist.destroy_process_group()
-    return 0 if not any(r["bad"] for r in res) else 1
+    return ranks_common.finish(dist, case, rank, world, bad)
 
 
 if __name__ == "__main__":

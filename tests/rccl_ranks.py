@@ -53,15 +53,12 @@ def _check_scale_rows(eng, orc, n, rows, cols):
 
 
 def run(case):
-    import torch.distributed as dist
-    from gossip_protocol_amd.dist import broadcast_bytes, sum_digests
-    from gossip_protocol_amd.scale import ScaleEngine, make_policy, nccl_unique_id
+    from gossip_protocol_amd.dist import sum_digests
+    from gossip_protocol_amd.scale import ScaleEngine, make_policy
+    from tests import ranks_common
     from tests.oracle_binding import PviewOracle, ScaleOracle
     from tests.oracle_binding import make_policy as oracle_policy
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = int(os.environ.get("LOCAL_RANK", "0"))
-    uid = broadcast_bytes(nccl_unique_id() if rank == 0 else None)
+    dist, rank, world, dev, uid = ranks_common.start()
     ticks = 12
     bad = []
     if case in ("pview_capacity", "rows_capacity"):
@@ -145,12 +142,7 @@ def run(case):
         bad.append(("xgmi_bytes", xgmi))
     eng.close()
     orc.close()
-    res = [None] * world
-    dist.all_gather_object(res, {"rank": rank, "bad": [str(b)[:300] for b in bad], "xgmi": xgmi})
-    if rank == 0:
-        print(json.dumps({"case": case, "world": world, "ranks": res}), flush=True)
-    dist.destroy_process_group()
-    return 0 if not any(r["bad"] for r in res) else 1
+    return ranks_common.finish(dist, case, rank, world, bad, xgmi=xgmi)
 
 
 def run_capacity(case, rank, world, dev, uid):

@@ -15,7 +15,6 @@ collective: per level each rank runs the rows and columns it holds and hops is a
 the numpy BFS over the oracle's rows (tests/reach_oracle.py).  torch.distributed (gloo) carries
 only the RCCL id and the verdicts.  Rank 0 prints one JSON line; exit status 0 means parity.
 """
-import json
 import os
 import sys
 
@@ -31,15 +30,11 @@ FIELDS = ("tick", "n", "age_limit", "direction", "alive", "sources", "reached", 
 
 
 def run(case):
-    import torch.distributed as dist
-    from gossip_protocol_amd.dist import broadcast_bytes
-    from gossip_protocol_amd.scale import ScaleEngine, nccl_unique_id
+    from gossip_protocol_amd.scale import ScaleEngine
+    from tests import ranks_common
     from tests import reach_oracle as ro
     from tests.oracle_binding import PviewOracle, ScaleOracle
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = int(os.environ.get("LOCAL_RANK", "0"))
-    uid = broadcast_bytes(nccl_unique_id() if rank == 0 else None)
+    dist, rank, world, dev, uid = ranks_common.start()
     pview = case == "pview_rows"
     if pview:
         from gossip_protocol_amd.pview import PviewEngine
@@ -79,12 +74,7 @@ def run(case):
                         bad.append(("info", t, lim, dname, name, got.info))
     eng.close()
     orc.close()
-    res = [None] * world
-    dist.all_gather_object(res, {"rank": rank, "bad": [str(b)[:300] for b in bad]})
-    if rank == 0:
-        print(json.dumps({"case": case, "world": world, "ranks": res}), flush=True)
-    dist.destroy_process_group()
-    return 0 if not any(r["bad"] for r in res) else 1
+    return ranks_common.finish(dist, case, rank, world, bad)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,6 @@ known at a get (MIN / SUM), so EVERY rank's result at ticks 0, 6, 12 and 13 must
 rule over the oracle's messages (tests/rumor_oracle.py).  torch.distributed (gloo) carries only
 the RCCL id and the verdicts.  Rank 0 prints one JSON line; exit status 0 means parity.
 """
-import json
 import os
 import sys
 
@@ -33,15 +32,11 @@ FIELDS = ("tick", "n", "rumor", "seed_tick", "sources", "alive", "known", "known
 
 
 def run(case):
-    import torch.distributed as dist
-    from gossip_protocol_amd.dist import broadcast_bytes
-    from gossip_protocol_amd.scale import ScaleEngine, nccl_unique_id
+    from gossip_protocol_amd.scale import ScaleEngine
+    from tests import ranks_common
     from tests import rumor_oracle as ru
     from tests.oracle_binding import PviewOracle, ScaleOracle
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = int(os.environ.get("LOCAL_RANK", "0"))
-    uid = broadcast_bytes(nccl_unique_id() if rank == 0 else None)
+    dist, rank, world, dev, uid = ranks_common.start()
     pview = case == "pview_rows"
     if pview:
         from gossip_protocol_amd.pview import PviewEngine
@@ -85,12 +80,7 @@ def run(case):
                     bad.append(("info", t, b, again, got.info))
     eng.rumor_close()
     eng.close()
-    res = [None] * world
-    dist.all_gather_object(res, {"rank": rank, "bad": [str(b)[:300] for b in bad]})
-    if rank == 0:
-        print(json.dumps({"case": case, "world": world, "ranks": res}), flush=True)
-    dist.destroy_process_group()
-    return 0 if not any(r["bad"] for r in res) else 1
+    return ranks_common.finish(dist, case, rank, world, bad)
 
 
 if __name__ == "__main__":

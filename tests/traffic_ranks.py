@@ -17,7 +17,6 @@ result at ticks 0, 12 and 20 -- each read twice -- must equal the numpy rule ove
 (tests/traffic_oracle.py).  torch.distributed (gloo) carries only the RCCL id and the verdicts.
 Rank 0 prints one JSON line; exit status 0 means parity.
 """
-import json
 import os
 import sys
 
@@ -32,15 +31,11 @@ CASES = {"columns_tiled": ("full", "main"), "rows": ("full", "main"), "pview_row
 
 
 def run(case):
-    import torch.distributed as dist
     from gossip_protocol_amd import traffic
-    from gossip_protocol_amd.dist import broadcast_bytes
-    from gossip_protocol_amd.scale import ScaleEngine, make_policy, nccl_unique_id
+    from gossip_protocol_amd.scale import ScaleEngine, make_policy
+    from tests import ranks_common
     from tests import traffic_oracle as to
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = int(os.environ.get("LOCAL_RANK", "0"))
-    uid = broadcast_bytes(nccl_unique_id() if rank == 0 else None)
+    dist, rank, world, dev, uid = ranks_common.start()
     kind, name = CASES[case]
     w = to.WORKLOADS[kind, name]
     pol = make_policy(**w["pol"]) if w["pol"] else None
@@ -74,12 +69,7 @@ def run(case):
                 bad.append(("info", t, again, got.info))
     eng.traffic_close()
     eng.close()
-    res = [None] * world
-    dist.all_gather_object(res, {"rank": rank, "bad": [str(b)[:300] for b in bad]})
-    if rank == 0:
-        print(json.dumps({"case": case, "world": world, "ranks": res}), flush=True)
-    dist.destroy_process_group()
-    return 0 if not any(r["bad"] for r in res) else 1
+    return ranks_common.finish(dist, case, rank, world, bad)
 
 
 if __name__ == "__main__":

@@ -144,6 +144,21 @@ _REACH = (ctypes.c_int, [ctypes.c_void_p, c_int32, c_int32, P(c_int32), c_int32,
                          P(ctypes.c_uint8), P(GspReachInfo)])
 
 
+REACH_MAX_SOURCES = 64
+
+
+class GspReachMultiInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("direction", c_int32),
+                ("alive", c_int32), ("n_sources", c_int32), ("alive_sources", c_int32),
+                ("depth", c_int32), ("levels", c_int32), ("reserved", c_int32), ("pairs", c_int64),
+                ("sum_hops", c_int64), ("kernel_ms", ctypes.c_double)]
+
+
+_REACH_MULTI = (ctypes.c_int, [ctypes.c_void_p, c_int32, c_int32, P(c_int32), c_int32, P(c_uint64),
+                               P(c_int32), P(c_int32), P(c_int32), P(c_int64), P(ctypes.c_uint32),
+                               c_int32, P(ctypes.c_uint8), P(GspReachMultiInfo)])
+
+
 class GspRumorInfo(ctypes.Structure):
     _fields_ = [("tick", c_int32), ("n", c_int32), ("rumor", c_int32), ("seed_tick", c_int32),
                 ("sources", c_int32), ("alive", c_int32), ("known", c_int32),
@@ -187,7 +202,7 @@ _TRAFFIC_GET = (ctypes.c_int, [ctypes.c_void_p] + [P(ctypes.c_uint32)] * 4 + [P(
 _TRAFFIC_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
 
 _PROBES = {                     # the probe entry points both scale engines export (probes.py)
-    "census": _CENSUS, "audit": _AUDIT, "reach": _REACH,
+    "census": _CENSUS, "audit": _AUDIT, "reach": _REACH, "reach_multi": _REACH_MULTI,
     "rumor_open": _RUMOR_OPEN, "rumor_seed": _RUMOR_SEED, "rumor_get": _RUMOR_GET, "rumor_close": _RUMOR_CLOSE,
     "detect_open": _DETECT_OPEN, "detect_get": _DETECT_GET, "detect_close": _DETECT_OPEN,
     "traffic_open": _TRAFFIC_OPEN, "traffic_get": _TRAFFIC_GET, "traffic_close": _TRAFFIC_CLOSE,

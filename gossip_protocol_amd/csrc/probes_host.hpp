@@ -1,6 +1,7 @@
 // gossip_protocol_amd/csrc/probes_host.hpp -- the host side of the six read-only probes of the two
 // scale-mode engines, on top of the engine core (engine_host.hpp): three snapshot probes of the
-// current tick (census, view audit, overlay reach) and three per-tick probes that ride along with
+// current tick (census, view audit, overlay reach -- reach in a single-source-set and a 64-tree
+// form, reach_run and reach_multi_run) and three per-tick probes that ride along with
 // step between open and close (rumor trace, detection ledger, traffic ledger).  The engines derive
 // from ProbeCore and pass themselves as E; kernels and their argument structs are in the
 // *_kernels.hpp of each probe.
@@ -28,6 +29,7 @@
 #include "detect_kernels.hpp"
 #include "engine_host.hpp"
 #include "reach_kernels.hpp"
+#include "reach_multi_kernels.hpp"
 #include "rumor_kernels.hpp"
 #include "traffic_kernels.hpp"
 
@@ -218,6 +220,25 @@ struct ReachBufs {
     }
 };
 
+// The multi-source reach state (gsp_scale_reach_multi / gsp_pview_reach_multi,
+// reach_multi_kernels.hpp), allocated by the first call and shared by every local shard: the three
+// 64-bit words per node, the two bitmaps the level kernel rewrites, the 64 cumulative per-tree
+// counters with their pinned mirror, and the sources' device copy.  hops[n_sources][n] comes with
+// the first call that asks for hops, stage[world][nodes] with a communicator.
+struct ReachMultiBufs {
+    DevBuf<uint64_t> seen, front, next, hot, open, stage;
+    DevBuf<uint32_t> count, hops;
+    DevBuf<int32_t> src;
+    uint32_t *h_count = nullptr;   // pinned, kReachMultiMax words
+    SpanTimer span;
+
+    void release() {
+        release_all(seen, front, next, hot, open, stage, count, hops, src, span);
+        if (h_count) (void)hipHostFree(h_count);
+        h_count = nullptr;
+    }
+};
+
 // The rumor trace (gsp_*_rumor_*, rumor_kernels.hpp), allocated by open and freed by close, shared
 // by every local shard.  `red` stages the all-reduced heard / known of a get across row-shard
 // ranks, so the device state itself is never summed twice.
@@ -270,6 +291,7 @@ struct ProbeCore : EngineCore {
     CensusBufs census;
     AuditBufs audit;
     ReachBufs reach;
+    ReachMultiBufs reach_multi;
     RumorBufs rumor;
     DetectBufs detect;
     TrafficBufs traffic;
@@ -287,7 +309,7 @@ inline int collect_timing(ProbeCore &c) {
 // events go back to the pool while it exists: engine_close then destroys every event once.
 inline void engine_close(ProbeCore &c) {
     for (TickTimer *t : {&c.rumor.timer, &c.detect.timer, &c.traffic.timer}) t->give_back(c);
-    release_all(c.census, c.audit, c.reach, c.rumor, c.detect, c.traffic);
+    release_all(c.census, c.audit, c.reach, c.reach_multi, c.rumor, c.detect, c.traffic);
     engine_close(static_cast<EngineCore &>(c));
 }
 
@@ -526,6 +548,158 @@ int reach_run(E &s, const char *fn, int32_t direction, int32_t age_limit, const 
     if (info) {
         *info = gsp_reach_info{T, s.p.n, age_limit, direction, alive, int32_t(level0), int32_t(reached),
                                depth, levels, sum_hops, 0.0};
+        GSP_HIP(b.span.elapsed(s, &info->kernel_ms));
+    }
+    return GSP_OK;
+}
+
+// The multi-source reach of the engine's current tick T (gossip.h, reach_multi_kernels.hpp): up to
+// 64 single-source BFS trees, tree b from sources[b], one launch per local shard and level for all
+// of them.  launch(shard, common, to) ORs that shard's share of level common.cur into next; with a
+// communicator every rank's next is all-gathered and ORed down (RCCL has no bitwise-OR
+// reduction), so every rank's level kernel admits and counts the same bits.  The level kernel
+// adds the nodes each tree just reached to 64 cumulative counters the host waits for: one host
+// wait per level, and the loop ends at the first level that sets no bit.  Every per-source output
+// comes from those counters; only seen and hops are read back from the device.
+template <class E, class Launch>
+int reach_multi_run(E &s, const char *fn, int32_t direction, int32_t age_limit, const int32_t *sources,
+                    int32_t n_sources, uint64_t *seen, int32_t *hops, int32_t *reached, int32_t *ecc,
+                    int64_t *sum_hops, uint32_t *level_sizes, int32_t level_cap, uint8_t *state,
+                    gsp_reach_multi_info *info, Launch launch) {
+    GSP_REQUIRE(direction == GSP_REACH_FROM || direction == GSP_REACH_TO, GSP_ERR_INVALID,
+                "%s: direction=%d is neither GSP_REACH_FROM (0) nor GSP_REACH_TO (1)", fn, direction);
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID, "%s: age_limit=%d outside [1,32]",
+                fn, age_limit);
+    GSP_REQUIRE(n_sources >= 1 && n_sources <= GSP_REACH_MAX_SOURCES, GSP_ERR_INVALID,
+                "%s: n_sources=%d outside [1,%d]", fn, n_sources, GSP_REACH_MAX_SOURCES);
+    if (int rc = check_ids(fn, "sources", sources, n_sources, s.p.n)) return rc;
+    GSP_REQUIRE(level_cap >= 0 || !level_sizes, GSP_ERR_INVALID, "%s: level_cap=%d", fn, level_cap);
+    const size_t n = size_t(s.p.n), words = reach_bitmap_words(s.p.n), nodes = reach_multi_nodes(s.p.n);
+    const size_t K = size_t(n_sources);
+    const int32_t T = s.tick;
+    ReachMultiBufs &b = s.reach_multi;
+    int world = 1;
+    if (s.comm) GSP_NCCL(ncclCommCount(s.comm, &world));
+    if (!b.span.ready) {               // first call
+        GSP_HIP(b.seen.alloc(nodes));
+        GSP_HIP(b.front.alloc(nodes));
+        GSP_HIP(b.next.alloc(nodes));
+        GSP_HIP(b.hot.alloc(words));
+        GSP_HIP(b.open.alloc(words));
+        GSP_HIP(b.count.alloc(kReachMultiMax));
+        GSP_HIP(b.src.alloc(kReachMultiMax));
+        if (s.comm) GSP_HIP(b.stage.alloc(size_t(world) * nodes));
+        if (!b.h_count)
+            GSP_HIP(hipHostMalloc(reinterpret_cast<void **>(&b.h_count), size_t(kReachMultiMax) * 4));
+        GSP_HIP(b.span.arm());
+    }
+    if (hops) GSP_HIP(b.hops.alloc(K * n));
+
+    uint64_t want = 0;
+    int32_t alive_sources = 0;
+    for (size_t i = 0; i < K; ++i)
+        if (node_state(s, T, size_t(sources[i])) == 1) {
+            want |= 1ull << i;
+            ++alive_sources;
+        }
+
+    ReachMultiLevelArgs lv{};
+    lv.n = s.p.n;
+    lv.tick = T;
+    lv.n_sources = n_sources;
+    lv.want = want;
+    lv.fail_tick = s.local[0].fail_tick.p;
+    lv.start_tick = s.joins ? s.local[0].start_tick.p : nullptr;
+    lv.seen = b.seen.p;
+    lv.front = b.front.p;
+    lv.next = b.next.p;
+    lv.hot = b.hot.p;
+    lv.open = b.open.p;
+    lv.count = b.count.p;
+    lv.hops = hops ? b.hops.p : nullptr;
+
+    ReachMultiCommon c{};
+    c.n = s.p.n;
+    c.tick = T;
+    c.age_limit = age_limit;
+    c.want = want;
+    c.seen = b.seen.p;
+    c.front = b.front.p;
+    c.next = b.next.p;
+    c.hot = b.hot.p;
+    c.open = b.open.p;
+
+    // per tree: the cumulative count as of the last level, and what the outputs are built from
+    uint32_t have[kReachMultiMax] = {0};
+    int32_t h_ecc[kReachMultiMax];
+    int64_t h_sum[kReachMultiMax] = {0};
+    std::fill(h_ecc, h_ecc + kReachMultiMax, -1);
+    if (level_sizes) std::fill(level_sizes, level_sizes + K * size_t(level_cap), 0u);
+
+    // admit what was ORed into next as `level` and count it per tree (waits for the stream)
+    auto admit = [&](uint32_t level, uint64_t *found) -> int {
+        lv.level = level;
+        GSP_HIP(launch_reach_multi_level(lv, s.st));
+        GSP_HIP(hipMemcpyAsync(b.h_count, b.count.p, size_t(kReachMultiMax) * 4, hipMemcpyDeviceToHost, s.st));
+        GSP_HIP(hipStreamSynchronize(s.st));
+        *found = 0;
+        for (size_t i = 0; i < K; ++i) {
+            const uint32_t got = b.h_count[i] - have[i];
+            have[i] = b.h_count[i];
+            if (!got) continue;
+            *found += got;
+            h_ecc[i] = int32_t(level);
+            h_sum[i] += int64_t(got) * int64_t(level);
+            if (level_sizes && level < uint32_t(level_cap)) level_sizes[i * size_t(level_cap) + level] = got;
+        }
+        return GSP_OK;
+    };
+
+    GSP_HIP(b.span.begin(s));
+    GSP_HIP(hipMemcpyAsync(b.src.p, sources, K * 4, hipMemcpyHostToDevice, s.st));
+    GSP_HIP(hipMemsetAsync(b.seen.p, 0, nodes * 8, s.st));
+    GSP_HIP(hipMemsetAsync(b.front.p, 0, nodes * 8, s.st));
+    GSP_HIP(hipMemsetAsync(b.next.p, 0, nodes * 8, s.st));
+    GSP_HIP(hipMemsetAsync(b.count.p, 0, size_t(kReachMultiMax) * 4, s.st));
+    if (hops) GSP_HIP(hipMemsetAsync(b.hops.p, 0xFF, K * n * 4, s.st));          // -1: not reached
+    GSP_HIP(launch_reach_multi_seed(b.src.p, lv, s.st));
+    uint64_t found = 0;
+    if (int rc = admit(0, &found)) return rc;
+    int32_t depth = -1, levels = 0;
+    uint32_t cur = 0;
+    while (found) {
+        depth = int32_t(cur);
+        for (auto &sh : s.local)
+            if (int rc = launch(sh, c, direction == GSP_REACH_TO)) return rc;
+        if (s.comm) {
+            GSP_NCCL(ncclAllGather(b.next.p, b.stage.p, nodes, ncclUint64, s.comm, s.st));
+            GSP_HIP(launch_reach_multi_fold(b.stage.p, world, nodes, b.next.p, s.st));
+        }
+        ++levels;
+        if (int rc = admit(cur + 1, &found)) return rc;
+        ++cur;
+    }
+    GSP_HIP(b.span.end(s));
+    if (seen) GSP_HIP(hipMemcpyAsync(seen, b.seen.p, n * 8, hipMemcpyDeviceToHost, s.st));
+    if (hops) GSP_HIP(hipMemcpyAsync(hops, b.hops.p, K * n * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    int32_t alive = 0;
+    for (size_t x = 0; x < n; ++x) {
+        const uint8_t st = node_state(s, T, x);
+        alive += st == 1;
+        if (state) state[x] = st;
+    }
+    int64_t pairs = 0, total = 0;
+    for (size_t i = 0; i < K; ++i) {
+        pairs += have[i];
+        total += h_sum[i];
+        if (reached) reached[i] = int32_t(have[i]);
+        if (ecc) ecc[i] = h_ecc[i];
+        if (sum_hops) sum_hops[i] = h_sum[i];
+    }
+    if (info) {
+        *info = gsp_reach_multi_info{T, s.p.n, age_limit, direction, alive, n_sources, alive_sources,
+                                     depth, levels, 0, pairs, total, 0.0};
         GSP_HIP(b.span.elapsed(s, &info->kernel_ms));
     }
     return GSP_OK;

@@ -714,6 +714,28 @@ int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const in
     });
 }
 
+// Multi-source reach of the current tick (reach_multi_run): the same shares as gsp_pview_reach.
+int gsp_pview_reach_multi(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
+                          int32_t n_sources, uint64_t *seen, int32_t *hops, int32_t *reached, int32_t *ecc,
+                          int64_t *sum_hops, uint32_t *level_sizes, int32_t level_cap, uint8_t *state,
+                          gsp_reach_multi_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_reach_multi: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::reach_multi_run(*s, "gsp_pview_reach_multi", direction, age_limit, sources, n_sources, seen,
+                                hops, reached, ecc, sum_hops, level_sizes, level_cap, state, info,
+                                [&](PvShard &sh, const gsp::ReachMultiCommon &c, bool to) -> int {
+        gsp::ReachMultiPviewArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.len = sh.len[s->tick & 1].p;
+        a.view = s->p.view;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_reach_multi_pview(a, to, s->st));
+        return GSP_OK;
+    });
+}
+
 // Rumor trace (rumor_*): a bounded inbox hears the senders of its receipt record, drain all every
 // entry of the segment.
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors) {

@@ -1,16 +1,12 @@
 // gossip_protocol_amd/csrc/reach_kernels.hip -- the overlay-reach kernels (reach_kernels.hpp).
 #include "reach_kernels.hpp"
-#include "scale_row.hpp"
+#include "reach_row.hpp"
 
 namespace gsp {
 namespace {
 
 __device__ __forceinline__ bool reach_alive(const ReachCommon &c, int32_t r) {
-    return (c.start_tick ? c.start_tick[r] : 0) <= c.tick && c.tick <= c.fail_tick[r];
-}
-
-__device__ __forceinline__ bool reach_bit(const uint64_t *map, uint32_t x) {
-    return (reinterpret_cast<const uint32_t *>(map)[x >> 5] >> (x & 31u)) & 1u;
+    return reach_alive_at(c.start_tick, c.fail_tick, c.tick, r);
 }
 
 // every writer of a launch stores the same cur + 1; the load only spares the atomic (a stale
@@ -55,22 +51,7 @@ __global__ void __launch_bounds__(256) reach_level_kernel(ReachCommon c, uint32_
     if (lane == 0 && found) atomicAdd(count, found);
 }
 
-// ---- full view -------------------------------------------------------------------------------
-// present & fresh of the two entries of a word: 1 in bit 0 / bit 16 (the census's arithmetic)
-__device__ __forceinline__ uint32_t reach_fresh(uint32_t w, uint32_t t5x2, uint32_t lim) {
-    const uint32_t pe = pk_min(w, 0x00010001u);                  // present: e != 0
-    const uint32_t age = pk_sub(t5x2, w) & 0x001F001Fu;          // (T - ts) mod 32
-    return pk_min(pk_subc(lim, age), pe);                        // age < age_limit
-}
-
-// the four words' flags as one bit per entry, entry q of the lane vector in bit q
-__device__ __forceinline__ uint32_t reach_pack(const uint32_t (&f)[4]) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) m |= ((f[i] | (f[i] >> 15)) & 3u) << (2 * i);
-    return m;
-}
-
+// ---- full view (reach_fresh / reach_pack: reach_row.hpp) --------------------------------------
 __device__ __forceinline__ void reach_or(uint32_t (&acc)[4], const uint4 &v, uint32_t t5x2, uint32_t lim) {
     acc[0] |= reach_fresh(v.x, t5x2, lim);
     acc[1] |= reach_fresh(v.y, t5x2, lim);
@@ -176,8 +157,7 @@ __global__ void __launch_bounds__(256) reach_scale_to_kernel(ReachScaleArgs a) {
 // hops words (TO: and todo bits) and one ballot, and walks only the selected rows, 64 slots at
 // a time.  Only the slots below len are read; an id >= n is dropped before it becomes an address.
 __device__ __forceinline__ bool reach_entry(const ReachPviewArgs &a, uint64_t e, uint32_t &id) {
-    id = uint32_t(e >> 32);
-    return id < uint32_t(a.c.n) && ((uint32_t(a.c.tick) - uint32_t(e)) & 31u) < uint32_t(a.c.age_limit);
+    return reach_entry_at(e, a.c.n, a.c.tick, a.c.age_limit, id);
 }
 
 // FROM (push): the frontier rows' fresh entries whose target is alive and unset

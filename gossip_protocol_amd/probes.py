@@ -6,6 +6,7 @@ from . import audit as _audit
 from . import census as _census
 from . import detect as _detect
 from . import reach as _reach
+from . import reach_multi as _reach_multi
 from . import rumor as _rumor
 from . import traffic as _traffic
 from ._lib import check, lib
@@ -45,6 +46,15 @@ class ProbeMethods:
         the ranks of a job."""
         fn, what = self._probe("reach")
         return _reach.run(fn, self._h, self.n, sources, direction, self._age_limit(age_limit), what)
+
+    def reach_multi(self, sources, direction="from", age_limit=None, hops=True, level_cap=256):
+        """Up to 64 single-source BFS trees over the graph of reach() in one call
+        (reach_multi.ReachMulti): row b of every array is reach(sources[b]).  hops=False leaves
+        the [n_sources, n] matrix out; level_cap bounds level_sizes.  age_limit defaults as for
+        reach().  Collective across the ranks of a job."""
+        fn, what = self._probe("reach_multi")
+        return _reach_multi.run(fn, self._h, self.n, sources, direction, self._age_limit(age_limit),
+                                hops, level_cap, what)
 
     def rumor_open(self, rumors=32):
         """Open a rumor trace of `rumors` (1..32) independent rumors (rumor.py): from now on

@@ -584,6 +584,52 @@ int gsp_scale_reach(gsp_scale *s, int32_t direction, int32_t age_limit, const in
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);
 
 /* ------------------------------------------------------------------------------------
+ * Multi-source reach: up to 64 exact single-source BFS trees in one sweep of the tables per
+ * level.  Graph, vertices, edge rule, direction, the age_limit range, aliveness and collectivity
+ * are those of "Overlay reach" above.  A node's state is one 64-bit word and bit b belongs to
+ * sources[b] alone: row b of every output equals what gsp_*_reach returns for the one-element
+ * source set {sources[b]}, at the cost of about one streaming pass per level for all trees.
+ *   sources     n_sources (1..GSP_REACH_MAX_SOURCES) ids in [0, n).  The same id may stand under
+ *               several bits; those bits get equal rows.  A source that is not alive at T leaves
+ *               its row empty: hops -1, reached 0, ecc -1, sum_hops 0.
+ *   seen[x]     n elements: bit b set iff x is reached from (FROM) / reaches (TO) sources[b]; the
+ *               source itself counts, at hop 0
+ *   hops[b * n + x]   int32, -1 where x is not alive or not reached by tree b
+ *   reached[b], ecc[b], sum_hops[b]   n_sources elements each: the nodes tree b reached, its
+ *               largest hop count, and the sum of its hops
+ *   level_sizes[b * level_cap + l]   for l < level_cap: the nodes at hop l of tree b (0 past its
+ *               ecc).  Levels >= level_cap are dropped from this array only.
+ *   state[x]    n elements, as in the census
+ * Any output may be NULL.  The result is the same, bit for bit, for every layout and number of
+ * shards: a level's launches only read what the previous level left and only OR into the next
+ * frontier.  One launch per local shard and level plus one host wait per level, for all trees
+ * together.  With a communicator the call is COLLECTIVE like gsp_*_reach: the next frontier of
+ * every rank is all-gathered and ORed after every level, and every rank gets the whole result.
+ * A bad argument returns GSP_ERR_INVALID before any launch; a pending capacity error returns
+ * GSP_ERR_CAPACITY as the other reads do.  The state (24 B + 2 bits per node; 4 B per node and
+ * source more once a call asks for hops) is allocated by the first call and freed at destroy.
+ * ---------------------------------------------------------------------------------- */
+#define GSP_REACH_MAX_SOURCES 64
+typedef struct {
+    int32_t tick, n, age_limit, direction;
+    int32_t alive;          /* nodes alive at T                                        */
+    int32_t n_sources;      /* as passed                                               */
+    int32_t alive_sources;  /* bits whose source is alive at T                         */
+    int32_t depth;          /* largest hop count over all sources; -1: no alive source */
+    int32_t levels;         /* level launches made                                     */
+    int32_t reserved;
+    int64_t pairs;          /* sum over sources of the nodes reached, source included  */
+    int64_t sum_hops;       /* sum of hops over those pairs                            */
+    double kernel_ms;       /* as gsp_reach_info                                       */
+} gsp_reach_multi_info;
+
+int gsp_scale_reach_multi(gsp_scale *s, int32_t direction, int32_t age_limit,
+                          const int32_t *sources, int32_t n_sources,
+                          uint64_t *seen, int32_t *hops, int32_t *reached, int32_t *ecc,
+                          int64_t *sum_hops, uint32_t *level_sizes, int32_t level_cap,
+                          uint8_t *state, gsp_reach_multi_info *info);
+
+/* ------------------------------------------------------------------------------------
  * Rumor trace: dissemination times over the messages the engine really delivers.  A trace
  * carries up to 32 independent rumors, the bits of one 32-bit word per node; while one is open,
  * every tick adds one small pull kernel per local shard over the tick's receiver CSR (JOINREPs
@@ -841,6 +887,12 @@ int gsp_pview_audit(gsp_pview *s, int32_t age_limit, uint32_t *size, uint32_t *d
 /* As gsp_scale_reach ("Overlay reach" above): a view is its row's out-edge list. */
 int gsp_pview_reach(gsp_pview *s, int32_t direction, int32_t age_limit, const int32_t *sources,
                     int32_t n_sources, int32_t *hops, uint8_t *state, gsp_reach_info *info);
+/* As gsp_scale_reach_multi ("Multi-source reach" above). */
+int gsp_pview_reach_multi(gsp_pview *s, int32_t direction, int32_t age_limit,
+                          const int32_t *sources, int32_t n_sources,
+                          uint64_t *seen, int32_t *hops, int32_t *reached, int32_t *ecc,
+                          int64_t *sum_hops, uint32_t *level_sizes, int32_t level_cap,
+                          uint8_t *state, gsp_reach_multi_info *info);
 /* As gsp_scale_rumor_* ("Rumor trace" above); a bounded inbox hears its `inbox` smallest senders. */
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors);
 int gsp_pview_rumor_seed(gsp_pview *s, int32_t rumor, const int32_t *sources, int32_t n_sources);

@@ -159,6 +159,20 @@ _REACH_MULTI = (ctypes.c_int, [ctypes.c_void_p, c_int32, c_int32, P(c_int32), c_
                                c_int32, P(ctypes.c_uint8), P(GspReachMultiInfo)])
 
 
+CLUSTER_MAX_OBSERVERS = 64
+
+
+class GspClusterInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("alive", c_int32),
+                ("n_observers", c_int32), ("alive_observers", c_int32), ("rows", c_int32),
+                ("reserved", c_int32), ("sum_degree", c_int64), ("sum_links", c_int64),
+                ("sum_mutual", c_int64), ("kernel_ms", ctypes.c_double)]
+
+
+_CLUSTER = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(c_int32), c_int32, P(c_uint64), P(ctypes.c_uint32),
+                           P(c_uint64), P(ctypes.c_uint32), P(ctypes.c_uint8), P(GspClusterInfo)])
+
+
 class GspRumorInfo(ctypes.Structure):
     _fields_ = [("tick", c_int32), ("n", c_int32), ("rumor", c_int32), ("seed_tick", c_int32),
                 ("sources", c_int32), ("alive", c_int32), ("known", c_int32),
@@ -203,6 +217,7 @@ _TRAFFIC_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
 
 _PROBES = {                     # the probe entry points both scale engines export (probes.py)
     "census": _CENSUS, "audit": _AUDIT, "reach": _REACH, "reach_multi": _REACH_MULTI,
+    "cluster": _CLUSTER,
     "rumor_open": _RUMOR_OPEN, "rumor_seed": _RUMOR_SEED, "rumor_get": _RUMOR_GET, "rumor_close": _RUMOR_CLOSE,
     "detect_open": _DETECT_OPEN, "detect_get": _DETECT_GET, "detect_close": _DETECT_OPEN,
     "traffic_open": _TRAFFIC_OPEN, "traffic_get": _TRAFFIC_GET, "traffic_close": _TRAFFIC_CLOSE,

@@ -1,12 +1,13 @@
-// gossip_protocol_amd/csrc/probes_host.hpp -- the host side of the six read-only probes of the two
-// scale-mode engines, on top of the engine core (engine_host.hpp): three snapshot probes of the
+// gossip_protocol_amd/csrc/probes_host.hpp -- the host side of the seven read-only probes of the
+// two scale-mode engines, on top of the engine core (engine_host.hpp): four snapshot probes of the
 // current tick (census, view audit, overlay reach -- reach in a single-source-set and a 64-tree
-// form, reach_run and reach_multi_run) and three per-tick probes that ride along with
-// step between open and close (rumor trace, detection ledger, traffic ledger).  The engines derive
+// form, reach_run and reach_multi_run -- and overlay clustering, cluster_run) and three per-tick
+// probes that ride along with step between open and close (rumor trace, detection ledger,
+// traffic ledger).  The engines derive
 // from ProbeCore and pass themselves as E; kernels and their argument structs are in the
 // *_kernels.hpp of each probe.
 //
-// What all six keep:
+// What all seven keep:
 //   - A probe reads the engine and writes only its own buffers, on the engine's stream: digests,
 //     rows and events are the same with any set of probes open, and step with none open makes the
 //     launches it makes without this header.
@@ -26,6 +27,7 @@
 
 #include "audit_kernels.hpp"
 #include "census_kernels.hpp"
+#include "cluster_kernels.hpp"
 #include "detect_kernels.hpp"
 #include "engine_host.hpp"
 #include "reach_kernels.hpp"
@@ -239,6 +241,22 @@ struct ReachMultiBufs {
     }
 };
 
+// The overlay-clustering state (gsp_scale_cluster / gsp_pview_cluster, cluster_kernels.hpp),
+// allocated by the first call and shared by every local shard: the member word per node, the
+// alive bitmap of the call (launch_audit_truth), the 64-bit counters and the observers' device
+// copy, with the host staging of member and the counters.
+struct ClusterBufs {
+    DevBuf<uint64_t> member;
+    DevBuf<uint8_t> alive;
+    DevBuf<unsigned long long> ctr;
+    DevBuf<int32_t> obs;
+    std::vector<uint64_t> h_member;
+    std::vector<unsigned long long> h_ctr;
+    SpanTimer span;
+
+    void release() { release_all(member, alive, ctr, obs, span); }
+};
+
 // The rumor trace (gsp_*_rumor_*, rumor_kernels.hpp), allocated by open and freed by close, shared
 // by every local shard.  `red` stages the all-reduced heard / known of a get across row-shard
 // ranks, so the device state itself is never summed twice.
@@ -286,12 +304,13 @@ struct TrafficBufs {
     void release() { release_all(led, watch_slot, psize); }
 };
 
-// The engine core with the six probes' state: what gsp_scale and gsp_pview derive from.
+// The engine core with the seven probes' state: what gsp_scale and gsp_pview derive from.
 struct ProbeCore : EngineCore {
     CensusBufs census;
     AuditBufs audit;
     ReachBufs reach;
     ReachMultiBufs reach_multi;
+    ClusterBufs cluster;
     RumorBufs rumor;
     DetectBufs detect;
     TrafficBufs traffic;
@@ -309,7 +328,7 @@ inline int collect_timing(ProbeCore &c) {
 // events go back to the pool while it exists: engine_close then destroys every event once.
 inline void engine_close(ProbeCore &c) {
     for (TickTimer *t : {&c.rumor.timer, &c.detect.timer, &c.traffic.timer}) t->give_back(c);
-    release_all(c.census, c.audit, c.reach, c.reach_multi, c.rumor, c.detect, c.traffic);
+    release_all(c.census, c.audit, c.reach, c.reach_multi, c.cluster, c.rumor, c.detect, c.traffic);
     engine_close(static_cast<EngineCore &>(c));
 }
 
@@ -700,6 +719,118 @@ int reach_multi_run(E &s, const char *fn, int32_t direction, int32_t age_limit, 
     if (info) {
         *info = gsp_reach_multi_info{T, s.p.n, age_limit, direction, alive, n_sources, alive_sources,
                                      depth, levels, 0, pairs, total, 0.0};
+        GSP_HIP(b.span.elapsed(s, &info->kernel_ms));
+    }
+    return GSP_OK;
+}
+
+// The overlay clustering of the engine's current tick T (gossip.h, cluster_kernels.hpp), for up
+// to 64 observers.  The prologue writes the call's alive bitmap; launch(shard, common, phase) runs
+// that shard's share -- its rows, its columns -- of the member pass (kClusterMembers) and then of
+// the link and mutual passes (kClusterLinks), which read the member words the first phase left.
+// With a communicator the member words are all-reduced between the phases.  SUM is exact there:
+// the words start from zero, and bit b of member[x] is written only by the one rank that holds
+// both observers[b]'s row and column x, so no two ranks ever add the same bit and no carry
+// exists.  The counters, zeroed per call, are all-reduced (SUM) in place after the second phase.
+// `rows` and the sums of the info come from the host's copy of member and the counters.
+template <class E, class Launch>
+int cluster_run(E &s, const char *fn, int32_t age_limit, const int32_t *observers, int32_t n_observers,
+                uint64_t *member, uint32_t *degree, uint64_t *links, uint32_t *mutual, uint8_t *state,
+                gsp_cluster_info *info, Launch launch) {
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID, "%s: age_limit=%d outside [1,32]", fn,
+                age_limit);
+    GSP_REQUIRE(n_observers >= 1 && n_observers <= GSP_CLUSTER_MAX_OBSERVERS, GSP_ERR_INVALID,
+                "%s: n_observers=%d outside [1,%d]", fn, n_observers, GSP_CLUSTER_MAX_OBSERVERS);
+    if (int rc = check_ids(fn, "observers", observers, n_observers, s.p.n)) return rc;
+    const size_t n = size_t(s.p.n), nodes = cluster_nodes(s.p.n), K = size_t(n_observers);
+    const size_t counters = kClusterCtrWords;
+    const int32_t T = s.tick;
+    ClusterBufs &b = s.cluster;
+    if (!b.span.ready) {               // first call
+        GSP_HIP(b.member.alloc(nodes));
+        GSP_HIP(b.alive.alloc(nodes / 8));
+        GSP_HIP(b.ctr.alloc(counters));
+        GSP_HIP(b.obs.alloc(kClusterMax));
+        // the prologue rewrites the bytes below (n + 7) / 8 per call; the rest stay 0
+        GSP_HIP(hipMemsetAsync(b.alive.p, 0, nodes / 8, s.st));
+        GSP_HIP(b.span.arm());
+    }
+    b.h_member.resize(n);
+    b.h_ctr.resize(counters);
+
+    uint64_t want = 0;
+    int32_t alive_observers = 0;
+    int32_t h_obs[kClusterMax] = {0};
+    for (size_t i = 0; i < K; ++i) {
+        h_obs[i] = observers[i];
+        if (node_state(s, T, size_t(observers[i])) == 1) {
+            want |= 1ull << i;
+            ++alive_observers;
+        }
+    }
+
+    ClusterCommon c{};
+    c.n = s.p.n;
+    c.tick = T;
+    c.age_limit = age_limit;
+    c.n_observers = n_observers;
+    c.want = want;
+    c.obs = b.obs.p;
+    c.alive = b.alive.p;
+    c.member = b.member.p;
+    c.ctr = b.ctr.p;
+
+    GSP_HIP(hipMemsetAsync(b.member.p, 0, nodes * 8, s.st));
+    GSP_HIP(hipMemsetAsync(b.ctr.p, 0, counters * 8, s.st));
+    GSP_HIP(b.span.begin(s));
+    // h_obs is on this frame: the stream is synchronised before the call returns
+    GSP_HIP(hipMemcpyAsync(b.obs.p, h_obs, size_t(kClusterMax) * 4, hipMemcpyHostToDevice, s.st));
+    AuditTruthArgs tr{};
+    tr.n = s.p.n;
+    tr.tick = T;
+    tr.fail_tick = s.local[0].fail_tick.p;
+    tr.start_tick = s.joins ? s.local[0].start_tick.p : nullptr;
+    tr.alive = b.alive.p;
+    tr.fp = nullptr;
+    GSP_HIP(launch_audit_truth(tr, s.st));
+    for (auto &sh : s.local)
+        if (int rc = launch(sh, c, int(kClusterMembers))) return rc;
+    if (s.comm) GSP_NCCL(ncclAllReduce(b.member.p, b.member.p, nodes, ncclUint64, ncclSum, s.comm, s.st));
+    for (auto &sh : s.local)
+        if (int rc = launch(sh, c, int(kClusterLinks))) return rc;
+    GSP_HIP(b.span.end(s));
+    if (s.comm) GSP_NCCL(ncclAllReduce(b.ctr.p, b.ctr.p, counters, ncclUint64, ncclSum, s.comm, s.st));
+    GSP_HIP(hipMemcpyAsync(b.h_member.data(), b.member.p, n * 8, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipMemcpyAsync(b.h_ctr.data(), b.ctr.p, counters * 8, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    int32_t alive = 0, rows = 0;
+    for (size_t x = 0; x < n; ++x) {
+        const uint8_t st = node_state(s, T, x);
+        alive += st == 1;
+        rows += b.h_member[x] != 0;
+        if (member) member[x] = b.h_member[x];
+        if (state) state[x] = st;
+    }
+    const unsigned long long *h = b.h_ctr.data();
+    int64_t sum_degree = 0, sum_links = 0, sum_mutual = 0;
+    for (size_t i = 0; i < K; ++i) {
+        unsigned long long d = 0, l = 0, m = 0;               // the copies of the counters, summed
+        for (size_t slot = 0; slot < size_t(kClusterSlots); ++slot) {
+            const unsigned long long *copy = h + slot * kClusterCounters * kClusterMax;
+            d += copy[size_t(kCluDegree) * kClusterMax + i];
+            l += copy[size_t(kCluLinks) * kClusterMax + i];
+            m += copy[size_t(kCluMutual) * kClusterMax + i];
+        }
+        sum_degree += int64_t(d);
+        sum_links += int64_t(l);
+        sum_mutual += int64_t(m);
+        if (degree) degree[i] = uint32_t(d);
+        if (links) links[i] = uint64_t(l);
+        if (mutual) mutual[i] = uint32_t(m);
+    }
+    if (info) {
+        *info = gsp_cluster_info{T, s.p.n, age_limit, alive, n_observers, alive_observers, rows, 0,
+                                 sum_degree, sum_links, sum_mutual, 0.0};
         GSP_HIP(b.span.elapsed(s, &info->kernel_ms));
     }
     return GSP_OK;

@@ -736,6 +736,26 @@ int gsp_pview_reach_multi(gsp_pview *s, int32_t direction, int32_t age_limit, co
     });
 }
 
+// Overlay clustering of the current tick (cluster_run): per phase every local shard runs its rows.
+int gsp_pview_cluster(gsp_pview *s, int32_t age_limit, const int32_t *observers, int32_t n_observers,
+                      uint64_t *member, uint32_t *degree, uint64_t *links, uint32_t *mutual, uint8_t *state,
+                      gsp_cluster_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_cluster: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::cluster_run(*s, "gsp_pview_cluster", age_limit, observers, n_observers, member, degree, links,
+                            mutual, state, info, [&](PvShard &sh, const gsp::ClusterCommon &c, int phase) -> int {
+        gsp::ClusterPviewArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.len = sh.len[s->tick & 1].p;
+        a.view = s->p.view;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_cluster_pview(a, phase, s->st));
+        return GSP_OK;
+    });
+}
+
 // Rumor trace (rumor_*): a bounded inbox hears the senders of its receipt record, drain all every
 // entry of the segment.
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors) {

@@ -813,6 +813,27 @@ int gsp_scale_reach_multi(gsp_scale *s, int32_t direction, int32_t age_limit, co
     });
 }
 
+// Overlay clustering of the current tick (cluster_run): per phase every local shard runs its rows
+// x columns -- the fused table, a column tile from col0, a row shard from row0.
+int gsp_scale_cluster(gsp_scale *s, int32_t age_limit, const int32_t *observers, int32_t n_observers,
+                      uint64_t *member, uint32_t *degree, uint64_t *links, uint32_t *mutual, uint8_t *state,
+                      gsp_cluster_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_cluster: NULL");
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::cluster_run(*s, "gsp_scale_cluster", age_limit, observers, n_observers, member, degree, links,
+                            mutual, state, info, [&](Shard &sh, const gsp::ClusterCommon &c, int phase) -> int {
+        gsp::ClusterScaleArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.stride = s->stride;
+        a.col0 = sh.col0;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_cluster_scale(a, phase, s->st));
+        return GSP_OK;
+    });
+}
+
 // Rumor trace (rumor_*): every entry of a receiver's segment is heard.
 int gsp_scale_rumor_open(gsp_scale *s, int32_t rumors) {
     return gsp::rumor_open(s, "gsp_scale_rumor_open", rumors);

@@ -1,9 +1,11 @@
 """The probe methods both scale engines have (gsp_scale_* / gsp_pview_* in
-include/gossip/gossip.h): census, view audit, overlay reach, rumor trace, detection ledger and
-traffic ledger.  The entry points differ only in their prefix, the class attribute `_abi`.
+include/gossip/gossip.h), seven probes: census, view audit, overlay reach (single-source-set and
+64-tree form), overlay clustering, rumor trace, detection ledger and traffic ledger.  The entry
+points differ only in their prefix, the class attribute `_abi`.
 """
 from . import audit as _audit
 from . import census as _census
+from . import cluster as _cluster
 from . import detect as _detect
 from . import reach as _reach
 from . import reach_multi as _reach_multi
@@ -55,6 +57,13 @@ class ProbeMethods:
         fn, what = self._probe("reach_multi")
         return _reach_multi.run(fn, self._h, self.n, sources, direction, self._age_limit(age_limit),
                                 hops, level_cap, what)
+
+    def cluster(self, observers, age_limit=None):
+        """Overlay clustering of up to 64 observers over the graph of reach() (cluster.Cluster):
+        per observer its out-degree, the links among its neighbours and the neighbours that list
+        it back.  age_limit defaults as for census().  Collective across the ranks of a job."""
+        fn, what = self._probe("cluster")
+        return _cluster.run(fn, self._h, self.n, observers, self._age_limit(age_limit), what)
 
     def rumor_open(self, rumors=32):
         """Open a rumor trace of `rumors` (1..32) independent rumors (rumor.py): from now on

@@ -630,6 +630,51 @@ int gsp_scale_reach_multi(gsp_scale *s, int32_t direction, int32_t age_limit,
                           uint8_t *state, gsp_reach_multi_info *info);
 
 /* ------------------------------------------------------------------------------------
+ * Overlay clustering: for up to 64 observers at once, how many of an observer's neighbours list
+ * each other and how many list the observer back.  Graph, vertices, edge rule, the age_limit
+ * range, aliveness and collectivity are those of "Overlay reach" above; bit b belongs to
+ * observers[b] alone, as in "Multi-source reach".  For an alive observer o = observers[b] with
+ * out-neighbour set N = {x : o -> x}:
+ *   observers   n_observers (1..GSP_CLUSTER_MAX_OBSERVERS) ids in [0, n).  The same id may stand
+ *               under several bits; those bits get equal results.  An observer that is not alive
+ *               at T gets zeros, and its bit is set nowhere.
+ *   member[x]   n elements: bit b set iff x is in N
+ *   degree[b]   |N|
+ *   links[b]    the ordered pairs (u, v) with u in N, v in N and u -> v, i.e. the sum over u in N
+ *               of |N(u) & N|: k (k - 1) where N is a clique, 0 where no two neighbours list each
+ *               other.  64-bit: it passes 2^32 at 65,536 nodes.
+ *   mutual[b]   the u in N with u -> o
+ *   state[x]    n elements, as in the census
+ * The local clustering coefficient of observers[b] is links[b] / (degree[b] (degree[b] - 1)).
+ * Any output may be NULL.  Every output is an integer built by OR and ADD alone, the same bit for
+ * bit for every layout and number of shards.  Two phases with the kernel boundary between them:
+ * the observers' rows are walked into member, then the rows with a non-zero member word are
+ * walked once (the full view: one streaming pass over those rows of the table).  With a
+ * communicator the call is COLLECTIVE: member is all-reduced between the phases and the counters
+ * after them, and every rank gets the whole result.  A bad argument returns GSP_ERR_INVALID
+ * before any launch; a pending capacity error returns GSP_ERR_CAPACITY as the other reads do.
+ * The state (8 B + 1 bit per node, and 96 KiB of counters) is allocated by the first call and
+ * freed at destroy.
+ * ---------------------------------------------------------------------------------- */
+#define GSP_CLUSTER_MAX_OBSERVERS 64
+typedef struct {
+    int32_t tick, n, age_limit;
+    int32_t alive;            /* nodes alive at T                                          */
+    int32_t n_observers;      /* as passed                                                 */
+    int32_t alive_observers;  /* bits whose observer is alive at T                         */
+    int32_t rows;             /* nodes whose member word is non-zero: the rows phase 2 walks */
+    int32_t reserved;
+    int64_t sum_degree;       /* sums over the bits                                        */
+    int64_t sum_links;
+    int64_t sum_mutual;
+    double kernel_ms;         /* HIP events around both phases (0: timing off)             */
+} gsp_cluster_info;
+
+int gsp_scale_cluster(gsp_scale *s, int32_t age_limit, const int32_t *observers,
+                      int32_t n_observers, uint64_t *member, uint32_t *degree, uint64_t *links,
+                      uint32_t *mutual, uint8_t *state, gsp_cluster_info *info);
+
+/* ------------------------------------------------------------------------------------
  * Rumor trace: dissemination times over the messages the engine really delivers.  A trace
  * carries up to 32 independent rumors, the bits of one 32-bit word per node; while one is open,
  * every tick adds one small pull kernel per local shard over the tick's receiver CSR (JOINREPs
@@ -893,7 +938,11 @@ int gsp_pview_reach_multi(gsp_pview *s, int32_t direction, int32_t age_limit,
                           uint64_t *seen, int32_t *hops, int32_t *reached, int32_t *ecc,
                           int64_t *sum_hops, uint32_t *level_sizes, int32_t level_cap,
                           uint8_t *state, gsp_reach_multi_info *info);
-/* As gsp_scale_rumor_* ("Rumor trace" above); a bounded inbox hears its `inbox` smallest senders. */
+/* As gsp_scale_cluster ("Overlay clustering" above); the rows walked are at most 64 x view. */
+int gsp_pview_cluster(gsp_pview *s, int32_t age_limit, const int32_t *observers,
+                      int32_t n_observers, uint64_t *member, uint32_t *degree, uint64_t *links,
+                      uint32_t *mutual, uint8_t *state, gsp_cluster_info *info);
+/* As gsp_scale_rumor_*("Rumor trace" above); a bounded inbox hears its `inbox` smallest senders. */
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors);
 int gsp_pview_rumor_seed(gsp_pview *s, int32_t rumor, const int32_t *sources, int32_t n_sources);
 int gsp_pview_rumor_get(gsp_pview *s, int32_t rumor, int32_t *heard, uint8_t *state,

@@ -173,6 +173,21 @@ _CLUSTER = (ctypes.c_int, [ctypes.c_void_p, c_int32, P(c_int32), c_int32, P(c_ui
                            P(c_uint64), P(ctypes.c_uint32), P(ctypes.c_uint8), P(GspClusterInfo)])
 
 
+COMPONENTS_WEAK, COMPONENTS_STRONG = 0, 1
+COMPONENTS_DEFAULT_SWEEPS = 65536
+
+
+class GspComponentsInfo(ctypes.Structure):
+    _fields_ = [("tick", c_int32), ("n", c_int32), ("age_limit", c_int32), ("kind", c_int32),
+                ("alive", c_int32), ("components", c_int32), ("largest", c_int32),
+                ("largest_label", c_int32), ("singletons", c_int32), ("sweeps", c_int32),
+                ("rounds", c_int32), ("converged", c_int32), ("kernel_ms", ctypes.c_double)]
+
+
+_COMPONENTS = (ctypes.c_int, [ctypes.c_void_p, c_int32, c_int32, c_int32, P(c_int32), P(ctypes.c_uint8),
+                              P(GspComponentsInfo)])
+
+
 class GspRumorInfo(ctypes.Structure):
     _fields_ = [("tick", c_int32), ("n", c_int32), ("rumor", c_int32), ("seed_tick", c_int32),
                 ("sources", c_int32), ("alive", c_int32), ("known", c_int32),
@@ -217,7 +232,7 @@ _TRAFFIC_CLOSE = (ctypes.c_int, [ctypes.c_void_p])
 
 _PROBES = {                     # the probe entry points both scale engines export (probes.py)
     "census": _CENSUS, "audit": _AUDIT, "reach": _REACH, "reach_multi": _REACH_MULTI,
-    "cluster": _CLUSTER,
+    "cluster": _CLUSTER, "components": _COMPONENTS,
     "rumor_open": _RUMOR_OPEN, "rumor_seed": _RUMOR_SEED, "rumor_get": _RUMOR_GET, "rumor_close": _RUMOR_CLOSE,
     "detect_open": _DETECT_OPEN, "detect_get": _DETECT_GET, "detect_close": _DETECT_OPEN,
     "traffic_open": _TRAFFIC_OPEN, "traffic_get": _TRAFFIC_GET, "traffic_close": _TRAFFIC_CLOSE,

@@ -211,6 +211,7 @@ int64_t gsp_struct_size(const char *name) {
     if (s == "gsp_reach_info") return int64_t(sizeof(gsp_reach_info));
     if (s == "gsp_reach_multi_info") return int64_t(sizeof(gsp_reach_multi_info));
     if (s == "gsp_cluster_info") return int64_t(sizeof(gsp_cluster_info));
+    if (s == "gsp_components_info") return int64_t(sizeof(gsp_components_info));
     if (s == "gsp_rumor_info") return int64_t(sizeof(gsp_rumor_info));
     if (s == "gsp_detect_info") return int64_t(sizeof(gsp_detect_info));
     if (s == "gsp_traffic_info") return int64_t(sizeof(gsp_traffic_info));

@@ -1,13 +1,13 @@
-// gossip_protocol_amd/csrc/probes_host.hpp -- the host side of the seven read-only probes of the
-// two scale-mode engines, on top of the engine core (engine_host.hpp): four snapshot probes of the
+// gossip_protocol_amd/csrc/probes_host.hpp -- the host side of the eight read-only probes of the
+// two scale-mode engines, on top of the engine core (engine_host.hpp): five snapshot probes of the
 // current tick (census, view audit, overlay reach -- reach in a single-source-set and a 64-tree
-// form, reach_run and reach_multi_run -- and overlay clustering, cluster_run) and three per-tick
-// probes that ride along with step between open and close (rumor trace, detection ledger,
-// traffic ledger).  The engines derive
+// form, reach_run and reach_multi_run -- overlay clustering, cluster_run, and overlay components,
+// components_run) and three per-tick probes that ride along with step between open and close
+// (rumor trace, detection ledger, traffic ledger).  The engines derive
 // from ProbeCore and pass themselves as E; kernels and their argument structs are in the
 // *_kernels.hpp of each probe.
 //
-// What all seven keep:
+// What all eight keep:
 //   - A probe reads the engine and writes only its own buffers, on the engine's stream: digests,
 //     rows and events are the same with any set of probes open, and step with none open makes the
 //     launches it makes without this header.
@@ -28,6 +28,7 @@
 #include "audit_kernels.hpp"
 #include "census_kernels.hpp"
 #include "cluster_kernels.hpp"
+#include "components_kernels.hpp"
 #include "detect_kernels.hpp"
 #include "engine_host.hpp"
 #include "reach_kernels.hpp"
@@ -257,6 +258,27 @@ struct ClusterBufs {
     void release() { release_all(member, alive, ctr, obs, span); }
 };
 
+// The overlay-components state (gsp_scale_components / gsp_pview_components,
+// components_kernels.hpp), allocated by the first call and shared by every local shard: arr holds
+// the kCompArrays n-length uint32 arrays, active the bitmap of the nodes still at work, ctr the
+// cumulative counters with their pinned mirror, h_label the host's copy of the labels and h_size
+// the component sizes the counts are made from.
+enum { kCompLab = 0, kCompFcol, kCompBcol, kCompPf, kCompPb, kCompIn, kCompOut, kCompComp, kCompArrays };
+struct ComponentsBufs {
+    DevBuf<uint32_t> arr;
+    DevBuf<uint64_t> active;
+    DevBuf<unsigned long long> ctr;
+    unsigned long long *h_ctr = nullptr;   // pinned, kCompCounters words
+    std::vector<uint32_t> h_label, h_size;
+    SpanTimer span;
+
+    void release() {
+        release_all(arr, active, ctr, span);
+        if (h_ctr) (void)hipHostFree(h_ctr);
+        h_ctr = nullptr;
+    }
+};
+
 // The rumor trace (gsp_*_rumor_*, rumor_kernels.hpp), allocated by open and freed by close, shared
 // by every local shard.  `red` stages the all-reduced heard / known of a get across row-shard
 // ranks, so the device state itself is never summed twice.
@@ -304,13 +326,14 @@ struct TrafficBufs {
     void release() { release_all(led, watch_slot, psize); }
 };
 
-// The engine core with the seven probes' state: what gsp_scale and gsp_pview derive from.
+// The engine core with the eight probes' state: what gsp_scale and gsp_pview derive from.
 struct ProbeCore : EngineCore {
     CensusBufs census;
     AuditBufs audit;
     ReachBufs reach;
     ReachMultiBufs reach_multi;
     ClusterBufs cluster;
+    ComponentsBufs components;
     RumorBufs rumor;
     DetectBufs detect;
     TrafficBufs traffic;
@@ -328,7 +351,7 @@ inline int collect_timing(ProbeCore &c) {
 // events go back to the pool while it exists: engine_close then destroys every event once.
 inline void engine_close(ProbeCore &c) {
     for (TickTimer *t : {&c.rumor.timer, &c.detect.timer, &c.traffic.timer}) t->give_back(c);
-    release_all(c.census, c.audit, c.reach, c.reach_multi, c.cluster, c.rumor, c.detect, c.traffic);
+    release_all(c.census, c.audit, c.reach, c.reach_multi, c.cluster, c.components, c.rumor, c.detect, c.traffic);
     engine_close(static_cast<EngineCore &>(c));
 }
 
@@ -831,6 +854,157 @@ int cluster_run(E &s, const char *fn, int32_t age_limit, const int32_t *observer
     if (info) {
         *info = gsp_cluster_info{T, s.p.n, age_limit, alive, n_observers, alive_observers, rows, 0,
                                  sum_degree, sum_links, sum_mutual, 0.0};
+        GSP_HIP(b.span.elapsed(s, &info->kernel_ms));
+    }
+    return GSP_OK;
+}
+
+// The overlay components of the engine's current tick T (gossip.h, components_kernels.hpp).  A
+// round is one sweep -- launch(shard, common) for every local shard: its rows, its columns --
+// then, with a communicator, the all-reduce of what the sweep moved (weak: lab, MIN; strong: fcol,
+// bcol and, after a turn's first sweep, has_in / has_out, MAX; every word only ever moves one
+// way, so MIN / MAX of the ranks' words is what one rank sweeping all shards would hold), the jump
+// kernel, and one host wait for the counters.  The jump runs on the reduced arrays, so every rank
+// reads the same checksum and takes the same branch.  Weak ends with the round that repeats the
+// checksum; strong then makes a turn, and ends when a turn leaves nobody unassigned.  The counts
+// of the info are made from the host's copy of the labels.
+template <class E, class Launch>
+int components_run(E &s, const char *fn, int32_t kind, int32_t age_limit, int32_t max_sweeps, int32_t *label,
+                   uint8_t *state, gsp_components_info *info, Launch launch) {
+    GSP_REQUIRE(kind == GSP_COMPONENTS_WEAK || kind == GSP_COMPONENTS_STRONG, GSP_ERR_INVALID,
+                "%s: kind=%d is neither GSP_COMPONENTS_WEAK (0) nor GSP_COMPONENTS_STRONG (1)", fn, kind);
+    GSP_REQUIRE(age_limit >= 1 && age_limit <= 32, GSP_ERR_INVALID, "%s: age_limit=%d outside [1,32]", fn,
+                age_limit);
+    GSP_REQUIRE(max_sweeps >= 0, GSP_ERR_INVALID, "%s: max_sweeps=%d is negative", fn, max_sweeps);
+    const int32_t cap = max_sweeps ? max_sweeps : GSP_COMPONENTS_DEFAULT_SWEEPS;
+    const size_t n = size_t(s.p.n), nodes = components_nodes(s.p.n);
+    const int32_t T = s.tick;
+    const bool weak = kind == GSP_COMPONENTS_WEAK;
+    ComponentsBufs &b = s.components;
+    if (!b.span.ready) {               // first call
+        GSP_HIP(b.arr.alloc(size_t(kCompArrays) * nodes));
+        GSP_HIP(b.active.alloc(nodes / 64));
+        GSP_HIP(b.ctr.alloc(kCompCounters));
+        if (!b.h_ctr)
+            GSP_HIP(hipHostMalloc(reinterpret_cast<void **>(&b.h_ctr), size_t(kCompCounters) * 8));
+        GSP_HIP(b.span.arm());
+    }
+    b.h_label.resize(n);
+    auto arr = [&](int which) { return b.arr.p + size_t(which) * nodes; };
+
+    CompCommon c{};
+    c.n = s.p.n;
+    c.tick = T;
+    c.age_limit = age_limit;
+    c.kind = kind;
+    c.fail_tick = s.local[0].fail_tick.p;
+    c.start_tick = s.joins ? s.local[0].start_tick.p : nullptr;
+    c.active = b.active.p;
+    c.lab = arr(kCompLab);
+    c.fcol = arr(kCompFcol);
+    c.bcol = arr(kCompBcol);
+    c.pf = arr(kCompPf);
+    c.pb = arr(kCompPb);
+    c.has_in = arr(kCompIn);
+    c.has_out = arr(kCompOut);
+    c.comp = arr(kCompComp);
+    c.ctr = b.ctr.p;
+
+    // the counters since the last wait (waits for the stream).  Only the n-length kernels count,
+    // and they run on the reduced arrays: every rank holds the same counters, nothing to reduce.
+    unsigned long long seen[kCompCounters] = {0}, got[kCompCounters] = {0};
+    int32_t sweeps = 0, rounds = 0;
+    auto wait = [&]() -> int {
+        GSP_HIP(hipMemcpyAsync(b.h_ctr, b.ctr.p, size_t(kCompCounters) * 8, hipMemcpyDeviceToHost, s.st));
+        GSP_HIP(hipStreamSynchronize(s.st));
+        ++rounds;
+        for (int i = 0; i < kCompCounters; ++i) {
+            got[i] = b.h_ctr[i] - seen[i];
+            seen[i] = b.h_ctr[i];
+        }
+        return GSP_OK;
+    };
+    auto reduce = [&](uint32_t *p, size_t words, ncclRedOp_t op) -> int {
+        if (s.comm) GSP_NCCL(ncclAllReduce(p, p, words, ncclUint32, op, s.comm, s.st));
+        return GSP_OK;
+    };
+    // one round; *sum: the checksum after it
+    auto round = [&](unsigned long long *sum) -> int {
+        for (auto &sh : s.local)
+            if (int rc = launch(sh, c)) return rc;
+        ++sweeps;
+        if (weak) {
+            if (int rc = reduce(c.lab, nodes, ncclMin)) return rc;
+        } else {
+            if (int rc = reduce(c.fcol, 2 * nodes, ncclMax)) return rc;               // fcol, bcol
+            if (c.first)
+                if (int rc = reduce(c.has_in, 2 * nodes, ncclMax)) return rc;         // has_in, has_out
+        }
+        GSP_HIP(launch_components_jump(c, s.st));
+        if (int rc = wait()) return rc;
+        *sum = got[kCompSum];
+        return GSP_OK;
+    };
+
+    GSP_HIP(b.span.begin(s));
+    GSP_HIP(hipMemsetAsync(b.ctr.p, 0, size_t(kCompCounters) * 8, s.st));
+    bool converged = false;
+    if (weak) {
+        GSP_HIP(launch_components_weak_init(c, s.st));
+        unsigned long long last = 0, sum = 0;
+        bool based = false;
+        while (!converged && sweeps < cap) {
+            if (int rc = round(&sum)) return rc;
+            if (!based) last = got[kCompBase];           // the init's checksum came with this wait
+            based = true;
+            converged = sum == last;
+            last = sum;
+        }
+    } else {
+        GSP_HIP(hipMemsetAsync(c.comp, 0xFF, nodes * 4, s.st));       // kCompNone
+        bool opening = true, turn = true;
+        unsigned long long last = 0, sum = 0;
+        while (!converged && sweeps < cap) {
+            if (turn) GSP_HIP(launch_components_turn(c, opening, s.st));
+            c.first = turn;
+            if (int rc = round(&sum)) return rc;
+            if (turn) {                                   // the turn's counters came with this wait
+                last = got[kCompBase];
+                converged = got[kCompLeft] == 0;
+            }
+            opening = false;
+            turn = sum == last;                           // an idle round: the turn is over
+            last = sum;
+        }
+        if (converged) GSP_HIP(launch_components_canon(c, s.st));
+    }
+    GSP_HIP(b.span.end(s));
+    if (converged)
+        GSP_HIP(hipMemcpyAsync(b.h_label.data(), c.lab, n * 4, hipMemcpyDeviceToHost, s.st));
+    GSP_HIP(hipStreamSynchronize(s.st));
+    int32_t alive = 0, components = 0, largest = 0, largest_label = -1, singletons = 0;
+    b.h_size.assign(converged ? n : 0, 0u);
+    for (size_t x = 0; x < n; ++x) {
+        const uint8_t st = node_state(s, T, x);
+        alive += st == 1;
+        if (state) state[x] = st;
+        // kCompNone is -1 as the caller's int32
+        if (label) label[x] = converged ? int32_t(b.h_label[x]) : (st == 1 ? int32_t(x) : -1);
+        if (converged && b.h_label[x] < n) ++b.h_size[b.h_label[x]];
+    }
+    for (size_t x = 0; x < b.h_size.size(); ++x) {
+        const uint32_t sz = b.h_size[x];
+        components += sz != 0;
+        singletons += sz == 1;
+        if (sz > uint32_t(largest)) {
+            largest = int32_t(sz);
+            largest_label = int32_t(x);
+        }
+    }
+    if (info) {
+        *info = gsp_components_info{T,       s.p.n,         age_limit,  kind,   alive,  components,
+                                    largest, largest_label, singletons, sweeps, rounds, converged ? 1 : 0,
+                                    0.0};
         GSP_HIP(b.span.elapsed(s, &info->kernel_ms));
     }
     return GSP_OK;

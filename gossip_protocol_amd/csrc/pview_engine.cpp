@@ -756,6 +756,26 @@ int gsp_pview_cluster(gsp_pview *s, int32_t age_limit, const int32_t *observers,
     });
 }
 
+// Overlay components of the current tick (components_run): per sweep every local shard runs its
+// rows.
+int gsp_pview_components(gsp_pview *s, int32_t kind, int32_t age_limit, int32_t max_sweeps, int32_t *label,
+                         uint8_t *state, gsp_components_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_pview_components: NULL");
+    if (int rc = gsp_pview_sync(s)) return rc;
+    return gsp::components_run(*s, "gsp_pview_components", kind, age_limit, max_sweeps, label, state, info,
+                               [&](PvShard &sh, const gsp::CompCommon &c) -> int {
+        gsp::CompPviewArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.len = sh.len[s->tick & 1].p;
+        a.view = s->p.view;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_components_pview(a, s->st));
+        return GSP_OK;
+    });
+}
+
 // Rumor trace (rumor_*): a bounded inbox hears the senders of its receipt record, drain all every
 // entry of the segment.
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors) {

@@ -834,6 +834,26 @@ int gsp_scale_cluster(gsp_scale *s, int32_t age_limit, const int32_t *observers,
     });
 }
 
+// Overlay components of the current tick (components_run): per sweep every local shard runs its
+// rows x columns -- the fused table, a column tile from col0, a row shard from row0.
+int gsp_scale_components(gsp_scale *s, int32_t kind, int32_t age_limit, int32_t max_sweeps, int32_t *label,
+                         uint8_t *state, gsp_components_info *info) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_components: NULL");
+    if (int rc = gsp_scale_sync(s)) return rc;
+    return gsp::components_run(*s, "gsp_scale_components", kind, age_limit, max_sweeps, label, state, info,
+                               [&](Shard &sh, const gsp::CompCommon &c) -> int {
+        gsp::CompScaleArgs a{};
+        a.c = c;
+        a.table = sh.table[s->tick & 1].p;
+        a.stride = s->stride;
+        a.col0 = sh.col0;
+        a.row0 = sh.row0;
+        a.rows = sh.rows;
+        GSP_HIP(gsp::launch_components_scale(a, s->st));
+        return GSP_OK;
+    });
+}
+
 // Rumor trace (rumor_*): every entry of a receiver's segment is heard.
 int gsp_scale_rumor_open(gsp_scale *s, int32_t rumors) {
     return gsp::rumor_open(s, "gsp_scale_rumor_open", rumors);

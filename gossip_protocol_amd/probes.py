@@ -1,11 +1,12 @@
 """The probe methods both scale engines have (gsp_scale_* / gsp_pview_* in
-include/gossip/gossip.h), seven probes: census, view audit, overlay reach (single-source-set and
-64-tree form), overlay clustering, rumor trace, detection ledger and traffic ledger.  The entry
-points differ only in their prefix, the class attribute `_abi`.
+include/gossip/gossip.h), eight probes: census, view audit, overlay reach (single-source-set and
+64-tree form), overlay clustering, overlay components, rumor trace, detection ledger and traffic
+ledger.  The entry points differ only in their prefix, the class attribute `_abi`.
 """
 from . import audit as _audit
 from . import census as _census
 from . import cluster as _cluster
+from . import components as _components
 from . import detect as _detect
 from . import reach as _reach
 from . import reach_multi as _reach_multi
@@ -64,6 +65,15 @@ class ProbeMethods:
         it back.  age_limit defaults as for census().  Collective across the ranks of a job."""
         fn, what = self._probe("cluster")
         return _cluster.run(fn, self._h, self.n, observers, self._age_limit(age_limit), what)
+
+    def components(self, kind="strong", age_limit=None, max_sweeps=0):
+        """The exact components of the graph of reach() (components.Components): kind "weak"
+        (either endpoint lists the other) or "strong" (mutually reachable); every alive node is
+        labelled with the smallest id of its component.  age_limit defaults as for reach();
+        max_sweeps caps the table sweeps (0: the library's default), and a capped call comes back
+        with converged False.  Collective across the ranks of a job."""
+        fn, what = self._probe("components")
+        return _components.run(fn, self._h, self.n, kind, self._age_limit(age_limit), max_sweeps, what)
 
     def rumor_open(self, rumors=32):
         """Open a rumor trace of `rumors` (1..32) independent rumors (rumor.py): from now on

@@ -675,6 +675,51 @@ int gsp_scale_cluster(gsp_scale *s, int32_t age_limit, const int32_t *observers,
                       uint32_t *mutual, uint8_t *state, gsp_cluster_info *info);
 
 /* ------------------------------------------------------------------------------------
+ * Overlay components: the exact weakly or strongly connected components of the overlay, i.e.
+ * how many pieces it has fallen into, how large each is and which one a node is in.  Graph,
+ * vertices, edge rule, the age_limit range (1..32), aliveness and collectivity are those of
+ * "Overlay reach" above: r -> x is an edge iff r and x are both alive at T, r's list holds x and
+ * (T - ts) mod 32 < age_limit.
+ *   kind        GSP_COMPONENTS_WEAK: the components of the undirected graph that has an edge
+ *               wherever either endpoint lists the other; GSP_COMPONENTS_STRONG: the strongly
+ *               connected components of the directed graph
+ *   label[x]    n elements, int32: for an alive x the smallest node id of x's component, -1 for a
+ *               node that is not alive.  This form does not depend on the order atomics land in,
+ *               on the layout or on the algorithm.
+ *   state[x]    n elements, as in the census
+ *   max_sweeps  a cap on table sweeps (one sweep: one pass of every local shard over its rows);
+ *               0 selects GSP_COMPONENTS_DEFAULT_SWEEPS.  Negative values are invalid.  When the
+ *               cap ends the loop early the call still returns GSP_OK, with info.converged = 0
+ *               and label unspecified for alive nodes.
+ * label, state and info may each be NULL.  The result is the same for every layout and number of
+ * shards.  A round is one sweep per local shard, one n-length kernel and one host wait; weak
+ * hooks tree roots under smaller roots and jumps pointers until a round changes nothing, strong
+ * trims and colours forwards and backwards on the nodes not yet assigned (components_kernels.hpp).
+ * With a communicator the call is COLLECTIVE: the label arrays are all-reduced (MIN / MAX) after
+ * every sweep, and every rank gets the whole result.  A bad argument returns GSP_ERR_INVALID
+ * before any launch; a pending capacity error returns GSP_ERR_CAPACITY as the other reads do.
+ * The state (32 B + 1 bit per node) is allocated by the first call and freed at destroy.
+ * ---------------------------------------------------------------------------------- */
+#define GSP_COMPONENTS_WEAK   0
+#define GSP_COMPONENTS_STRONG 1
+#define GSP_COMPONENTS_DEFAULT_SWEEPS 65536
+typedef struct {
+    int32_t tick, n, age_limit, kind;
+    int32_t alive;          /* nodes alive at T                                            */
+    int32_t components;     /* distinct labels                                             */
+    int32_t largest;        /* nodes of the largest component; 0 with no alive node        */
+    int32_t largest_label;  /* its label (the smallest among equals); -1 with no alive node */
+    int32_t singletons;     /* components of one node                                      */
+    int32_t sweeps;         /* table sweeps made                                           */
+    int32_t rounds;         /* host waits made                                             */
+    int32_t converged;      /* 0: max_sweeps ended the loop; the four counts above are 0 / -1 */
+    double kernel_ms;       /* as gsp_reach_info                                           */
+} gsp_components_info;
+
+int gsp_scale_components(gsp_scale *s, int32_t kind, int32_t age_limit, int32_t max_sweeps,
+                         int32_t *label, uint8_t *state, gsp_components_info *info);
+
+/* ------------------------------------------------------------------------------------
  * Rumor trace: dissemination times over the messages the engine really delivers.  A trace
  * carries up to 32 independent rumors, the bits of one 32-bit word per node; while one is open,
  * every tick adds one small pull kernel per local shard over the tick's receiver CSR (JOINREPs
@@ -942,6 +987,9 @@ int gsp_pview_reach_multi(gsp_pview *s, int32_t direction, int32_t age_limit,
 int gsp_pview_cluster(gsp_pview *s, int32_t age_limit, const int32_t *observers,
                       int32_t n_observers, uint64_t *member, uint32_t *degree, uint64_t *links,
                       uint32_t *mutual, uint8_t *state, gsp_cluster_info *info);
+/* As gsp_scale_components ("Overlay components" above). */
+int gsp_pview_components(gsp_pview *s, int32_t kind, int32_t age_limit, int32_t max_sweeps,
+                         int32_t *label, uint8_t *state, gsp_components_info *info);
 /* As gsp_scale_rumor_*("Rumor trace" above); a bounded inbox hears its `inbox` smallest senders. */
 int gsp_pview_rumor_open(gsp_pview *s, int32_t rumors);
 int gsp_pview_rumor_seed(gsp_pview *s, int32_t rumor, const int32_t *sources, int32_t n_sources);

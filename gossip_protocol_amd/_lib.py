@@ -313,6 +313,7 @@ SIGNATURES = {
     "gsp_scale_create_group_layout": (ctypes.c_int, [P(GspScaleParams), ctypes.c_int, c_int32,
                                                      c_int32, P(ctypes.c_void_p)]),
     "gsp_scale_layout": (ctypes.c_int, [ctypes.c_void_p, P(c_int32), P(c_int32), P(c_int64)]),
+    "gsp_scale_sweep": (ctypes.c_int, [ctypes.c_void_p, P(c_int32), P(c_int32)]),
     "gsp_scale_hip_stream": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_void_p)]),
     "gsp_pview_create": (ctypes.c_int, [P(GspPviewParams), ctypes.c_int, P(ctypes.c_void_p)]),
     "gsp_pview_create_rank": (ctypes.c_int, [P(GspPviewParams), ctypes.c_int, c_int32, c_int32,

@@ -73,7 +73,9 @@ struct gsp_scale : gsp::ProbeCore {
     int32_t sweep_seg = gsp::kSweepMaxSeg;   // the sweep defers rows with more messages
     std::vector<Shard> local;  // shards held by this engine (1, or G for an in-process group)
     gsp::DevBuf<gsp::ScaleTickArgs> long_tpl;   // [local][2]: every tile's args by tick parity
-                                                // (scale_long_kernel)
+                                                // (scale_sweep_kernel, scale_long_kernel)
+    std::vector<gsp::ScaleTickArgs> sweep_tiles;   // the tick's host-side args of every local tile
+                                                   // (launch_scale_sweep's checks, the count launches)
 
     gsp::ScaleTickArgs args(Shard &sh, int32_t t) const {
         gsp::ScaleTickArgs a{};
@@ -129,6 +131,7 @@ struct gsp_scale : gsp::ProbeCore {
         a.ev = sh.ev.args();
         // the rows this tile's CSR defers (k > kMaxSegment): appended by the CSR's owner only
         a.long_list = owns_csr(sh) ? long_list(sh, t) : nullptr;
+        a.appends = owns_csr(sh) ? 1 : 0;       // the tile table keeps this where it fills the lists in
         if (sweep && merge == 1) {
             a.sweep = sweep;
             a.sweep_seg = sweep_seg;
@@ -337,12 +340,13 @@ gsp::JoinForm join_form(const gsp_scale *s) {
             gsp::kDigDropped, size_t(s->stride) * sizeof(uint16_t)};
 }
 
-// scale_long_kernel's tile table: each tile's args at both tick parities (digest base at tick
-// 0, every tile reading its CSR owner's deferred-row list).  The long kernel patches only
-// tick, drop_pct, drop_prev and the digest offset per tick (scale_kernels.hip,
-// scale_long_kernel); every other field is read from here, so the table is rebuilt whenever
-// a field it copies can change after create (gsp_scale_set_cache_policy: nt_own / nt_src /
-// pipe).  An args field that changes per tick must join the kernel's patch list instead.
+// The tile table of scale_sweep_kernel and scale_long_kernel: each tile's args at both tick
+// parities (digest base at tick 0, every tile reading its CSR owner's deferred-row lists;
+// `appends` keeps saying which tile fills them in).  The kernels patch only tick, drop_pct,
+// drop_prev and the digest offset per tick (tile_args, scale_row.hpp); every other field is
+// read from here, so the table is rebuilt whenever a field it copies can change after create
+// (gsp_scale_set_cache_policy: nt_own / nt_src / pipe; gsp_scale_set_merge: the sweep fields).
+// An args field that changes per tick must join ScaleTickVals and tile_args instead.
 int upload_long_tpl(gsp_scale *s) {
     std::vector<gsp::ScaleTickArgs> tpl;
     for (Shard &sh : s->local)
@@ -557,16 +561,23 @@ int gsp_scale_step(gsp_scale *s, int32_t ticks) {
                     a.psize = s->owner(sh).cnt_total[(t + 1) & 1].p;
                 })) return rc;
         if (s->timing) GSP_HIP(hipEventRecord(tm.b, s->st));
-        for (Shard &sh : s->local)
-            GSP_HIP(gsp::launch_scale_tick(s->args(sh, t), s->sliced, s->merge, s->st));
-        if (s->sweep && s->merge == 1) {      // the sweep's per-sub-slab member counts -> cnt_cur
-            if (s->shared) GSP_HIP(gsp::launch_sweep_counts(s->args(s->local[0], t), int32_t(s->local.size()), s->st));
-            else for (Shard &sh : s->local) GSP_HIP(gsp::launch_sweep_counts(s->args(sh, t), 1, s->st));
+        if (s->sweep && s->merge == 1) {
+            // the sub-slab sweep: every local tile in one launch (the kernel reads each tile's
+            // args from the tile table), then its per-sub-slab member counts -> cnt_cur
+            std::vector<gsp::ScaleTickArgs> &tiles = s->sweep_tiles;   // reused: no allocation per tick
+            tiles.clear();
+            for (Shard &sh : s->local) tiles.push_back(s->args(sh, t));
+            GSP_HIP(gsp::launch_scale_sweep(tiles.data(), int32_t(tiles.size()), s->long_tpl.p, s->st));
+            if (s->shared) GSP_HIP(gsp::launch_sweep_counts(tiles[0], int32_t(tiles.size()), s->st));
+            else for (const gsp::ScaleTickArgs &a : tiles) GSP_HIP(gsp::launch_sweep_counts(a, 1, s->st));
+        } else {
+            for (Shard &sh : s->local)
+                GSP_HIP(gsp::launch_scale_tick(s->args(sh, t), s->sliced, s->merge, s->st));
         }
-        // the rows with more than kMaxSegment messages the launches above deferred (usually
-        // none: one short launch per tick)
+        // the rows the launches above deferred (usually none: one short launch per tick); the
+        // tiles of a shared CSR, or a single tile, have one pair of lists
         GSP_HIP(gsp::launch_scale_long(s->args(s->local[0], t), s->long_tpl.p, int32_t(s->local.size()),
-                                       s->sliced, s->st));
+                                       s->sliced, s->shared || s->local.size() == 1, s->st));
         if (s->timing) {
             GSP_HIP(hipEventRecord(tm.c, s->st));
             s->pending.push_back(tm);
@@ -693,6 +704,13 @@ int gsp_scale_set_cache_policy(gsp_scale *s, int32_t policy) {
 int gsp_scale_set_merge(gsp_scale *s, int32_t packed) {
     GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_set_merge: NULL");
     s->merge = packed ? 1 : 0;
+    return upload_long_tpl(s);         // the table copies the sweep fields args() sets for merge 1
+}
+
+int gsp_scale_sweep(gsp_scale *s, int32_t *width, int32_t *seg) {
+    GSP_REQUIRE(s, GSP_ERR_INVALID, "gsp_scale_sweep: NULL");
+    if (width) *width = s->merge == 1 ? s->sweep : 0;
+    if (seg) *seg = s->sweep_seg;
     return GSP_OK;
 }
 

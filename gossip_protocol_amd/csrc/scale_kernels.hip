@@ -554,7 +554,7 @@ __global__ void __launch_bounds__(kScaleBlock) scale_tick_kernel(ScaleTickArgs a
 
 // The sub-slab sweep of a column tile (slice form, plain protocol; DESIGN.md "Column tiles"):
 // the tile's stride columns are cut into stride / W sub-slabs of W = 512 * kV columns and the
-// grid walks them sub-slab-major (blockIdx = sub-slab * batches + batch), so that between two
+// grid walks them sub-slab-major (within a tile: item = sub-slab * batches + batch), so that between two
 // reads of a previous-table line the chip touches one sub-slab of prev and one of cur, which
 // the Infinity Cache holds.  A work item is one wave on (row, sub-slab): a workgroup takes
 // kSweepBatch consecutive rows of one sub-slab, 16 per wave, with no barrier and no LDS on
@@ -568,15 +568,25 @@ __global__ void __launch_bounds__(kScaleBlock) scale_tick_kernel(ScaleTickArgs a
 //             plain store per (sub-slab, row) to cnt_sub, summed by sweep_count_kernel; digest
 //             sums kept in registers over the wave's rows and added once, when non-zero; the
 //             per-row quantities (rounds, merges, delivered, own_hb) by the sub-slab-0 item
-// 5 waves per SIMD (96 VGPRs, 10 dwords of scratch for values the row loop does not touch):
+// 5 waves per SIMD (96 VGPRs; 9 dwords spilled, in a 40-byte scratch frame of 10 dwords, for
+// values the row loop does not touch):
 // measured at config 3 against 4 waves (107 VGPRs, no scratch) and 6 (80 VGPRs, 26 dwords):
 // 6.21 ms per tick against 7.07 and 6.97 (DESIGN.md "Column tiles").
+// One launch runs every local tile of the tick: the grid is tile-major, then sub-slab-major, then
+// batch (gridDim = ntiles * sub-slabs * batches; the tiles agree in rows and stride), so the
+// order inside a tile is the one above and tile g + 1's first sub-slab fills the CUs that tile
+// g's last one frees.  A workgroup's tile is wave-uniform: its args are scalar loads from the tile
+// table (tile_args), all issued before the first store.
 template <bool kNtCur>
-__global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_eu(5, 8))) scale_sweep_kernel(ScaleTickArgs a) {
+__global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_eu(5, 8)))
+scale_sweep_kernel(const ScaleTickArgs *__restrict__ tpl, int32_t ntiles, ScaleTickVals tv) {
     constexpr int W = kSweepWidth;
     const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t per_tile = int32_t(gridDim.x) / ntiles;
+    const int32_t tile = int32_t(blockIdx.x) / per_tile, item = int32_t(blockIdx.x) - tile * per_tile;
+    const ScaleTickArgs a = tile_args(tpl, tile, tv);
     const int32_t batches = (a.rows + kSweepBatch - 1) / kSweepBatch;
-    const int32_t sub = int32_t(blockIdx.x) / batches, batch = int32_t(blockIdx.x) - sub * batches;
+    const int32_t sub = item / batches, batch = item - sub * batches;
     if (*a.err) return;
     const int32_t t = a.tick;
     const int32_t lr0 = batch * kSweepBatch + wave * (kSweepBatch / 4);
@@ -612,7 +622,7 @@ __global__ void __launch_bounds__(kScaleBlock) __attribute__((amdgpu_waves_per_e
             const int32_t k = int32_t(lane_of(uint32_t(m_k), i));
             if (k < 0) continue;
             if (k <= a.sweep_seg) break;
-            if (sub == 0 && lane == 0) defer_row(k > kMaxSegment ? a.long_list : a.mid_list, lr0 + i);
+            if (sub == 0 && a.appends && lane == 0) defer_row(k > kMaxSegment ? a.long_list : a.mid_list, lr0 + i);
         }
         return i;
     };
@@ -736,29 +746,38 @@ __global__ void __launch_bounds__(256) sweep_count_kernel(ScaleTickArgs a, int32
 }
 
 // The rows the tick kernels deferred (k > kMaxSegment), after every tick-kernel launch of the
-// tick: tile g's args are its template of this tick's parity (made by the host, upload_long_tpl
-// in scale_engine.cpp) with the tick's own fields patched below -- tick, drop_pct, drop_prev,
-// the digest offset; a per-tick args field not in that list must be added there; each tile's list is its CSR's (the tiles of an in-process group share
-// one).  Launched once per tick; without a deferred row every workgroup reads the counts and
-// exits.  It also clears the lists of the next tick's parity.
+// tick: tile g's args come from the tile table (made by the host, upload_long_tpl in
+// scale_engine.cpp) through tile_args, which patches the tick's own fields; each tile's list is
+// its CSR's.  shared: the tiles share one CSR (an in-process group, or one tile), so every
+// tile's lists are tile 0's: their counts are read once, and with both at zero -- the usual
+// tick -- no tile's args are loaded at all.  Launched once per tick.  It also clears the lists
+// of the next tick's parity.
 template <bool kSlice, bool kTfail, bool kSwim>
 __global__ void __launch_bounds__(kScaleBlock) scale_long_kernel(ScaleTickArgs a, const ScaleTickArgs *tpl,
-                                                                 int32_t ntiles) {
+                                                                 int32_t ntiles, int32_t shared) {
+    constexpr bool kMid = kSlice && !kTfail && !kSwim;
     const int32_t t = a.tick;
-    for (int32_t g = 0; g < ntiles; ++g) {
-        ScaleTickArgs ag = tpl[2 * g + (t & 1)];
-        ag.tick = t;
-        ag.drop_pct = a.drop_pct;
-        ag.drop_prev = a.drop_prev;
-        ag.dig += size_t(t) * kDigSlots * kDigFields;
-        const int32_t cnt = ag.long_list[0];
+    const ScaleTickVals tv = tick_vals(a);
+    int32_t cnt = 0, mid = 0;
+    if (shared) {
+        const ScaleTickArgs &own = tpl[t & 1];
+        cnt = own.long_list[0];
+        if (kMid && own.mid_list) mid = own.mid_list[0];
+    }
+    // shared lists, both empty: no tile has a row to run (uniform over the grid)
+    const int32_t run_tiles = (shared && !(cnt | mid)) ? 0 : ntiles;
+    for (int32_t g = 0; g < run_tiles; ++g) {
+        const ScaleTickArgs ag = tile_args(tpl, g, tv);
+        if (!shared) {
+            cnt = ag.long_list[0];
+            mid = (kMid && ag.mid_list) ? ag.mid_list[0] : 0;
+        }
         for (int32_t i = int32_t(blockIdx.x); i < cnt; i += int32_t(gridDim.x)) {
             scale_tick_row<false, kSlice, 1, 0, false, kTfail, kSwim, true>(ag, ag.long_list[1 + i]);
             __syncthreads();                    // the row's LDS is read to its end
         }
         // the rows the sub-slab sweep left to the block form (kSweepMaxSeg < k <= kMaxSegment)
-        if constexpr (kSlice && !kTfail && !kSwim) {
-            const int32_t mid = ag.mid_list ? ag.mid_list[0] : 0;
+        if constexpr (kMid) {
             for (int32_t i = int32_t(blockIdx.x); i < mid; i += int32_t(gridDim.x)) {
                 scale_tick_row<false, true, 1, 0, false, false, false, false>(ag, ag.mid_list[1 + i]);
                 __syncthreads();
@@ -766,7 +785,7 @@ __global__ void __launch_bounds__(kScaleBlock) scale_long_kernel(ScaleTickArgs a
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int32_t g = 0; g < ntiles; ++g) {
+        for (int32_t g = 0; g < (shared ? 1 : ntiles); ++g) {
             const ScaleTickArgs &nx = tpl[2 * g + ((t + 1) & 1)];
             nx.long_list[0] = 0;
             if (nx.mid_list) nx.mid_list[0] = 0;
@@ -1008,17 +1027,30 @@ void launch_tick_policy(const ScaleTickArgs &a, int policy, size_t lds, hipStrea
     }
 }
 
-// one launch of the sub-slab sweep over a tile (a.sweep = W); nt_own: non-temporal stores of cur
-hipError_t launch_scale_sweep(const ScaleTickArgs &a, hipStream_t st) {
+// one launch of the sub-slab sweep over every local tile (sweep = W); nt_own: non-temporal
+// stores of cur.  The kernel cuts the grid into equal tiles and one LDS size and one store
+// policy serve the launch, so the tiles must agree in what decides them.
+hipError_t launch_scale_sweep(const ScaleTickArgs *tiles, int32_t ntiles, const ScaleTickArgs *tpl,
+                              hipStream_t st) {
+    if (ntiles < 1 || !tiles || !tpl) return hipErrorInvalidValue;
+    const ScaleTickArgs &a = tiles[0];
     const int32_t W = a.sweep;
-    if (W != kSweepWidth || a.stride % W || a.sweep_seg < 1 || a.sweep_seg > kSweepMaxSeg || !a.cnt_sub || !a.bitmap || a.csr_slot ||
-        a.tfail > 0 || a.swim > 0 || a.start_tick)
-        return hipErrorInvalidValue;
-    const int64_t blocks = (a.stride / W) * ((int64_t(a.rows) + kSweepBatch - 1) / kSweepBatch);
+    for (int32_t g = 0; g < ntiles; ++g) {
+        const ScaleTickArgs &x = tiles[g];
+        if (x.sweep != kSweepWidth || x.stride % W || x.sweep_seg < 1 || x.sweep_seg > kSweepMaxSeg || !x.cnt_sub ||
+            !x.bitmap || x.csr_slot || x.tfail > 0 || x.swim > 0 || x.start_tick || x.fanout < 1 || x.fanout > 16)
+            return hipErrorInvalidValue;
+        if (x.rows != a.rows || x.stride != a.stride || x.rows < 1 || x.tick != a.tick || x.nt_own != a.nt_own ||
+            (x.ev.buf != nullptr) != (a.ev.buf != nullptr))
+            return hipErrorInvalidValue;
+    }
+    const int64_t blocks = int64_t(ntiles) * (a.stride / W) * ((int64_t(a.rows) + kSweepBatch - 1) / kSweepBatch);
+    if (blocks > INT32_MAX) return hipErrorInvalidValue;
     const dim3 grid{unsigned(blocks)}, block(kScaleBlock);
     const size_t lds = a.ev.buf ? size_t(4) * size_t(W) * 4 : 0;
-    if (a.nt_own) hipLaunchKernelGGL((scale_sweep_kernel<true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((scale_sweep_kernel<false>), grid, block, lds, st, a);
+    const ScaleTickVals tv = tick_vals(a);
+    if (a.nt_own) hipLaunchKernelGGL((scale_sweep_kernel<true>), grid, block, lds, st, tpl, ntiles, tv);
+    else hipLaunchKernelGGL((scale_sweep_kernel<false>), grid, block, lds, st, tpl, ntiles, tv);
     return hipGetLastError();
 }
 
@@ -1031,7 +1063,7 @@ hipError_t launch_sweep_counts(const ScaleTickArgs &a, int32_t tiles, hipStream_
 
 hipError_t launch_scale_tick(const ScaleTickArgs &a, bool slice, int merge, hipStream_t st) {
     if (a.stride % kChunk || a.fanout < 1 || a.fanout > 16) return hipErrorInvalidValue;
-    if (slice && merge == 1 && a.sweep) return launch_scale_sweep(a, st);
+    if (slice && merge == 1 && a.sweep) return hipErrorInvalidValue;   // launch_scale_sweep runs those tiles
     const size_t lds = scale_lds_bytes(a.stride, slice, a.ev.buf != nullptr) + size_t(a.lds_pad);
     const int policy = (a.nt_own ? 1 : 0) | (a.nt_src ? 2 : 0);
     if (slice) {
@@ -1045,20 +1077,21 @@ hipError_t launch_scale_tick(const ScaleTickArgs &a, bool slice, int merge, hipS
 }
 
 hipError_t launch_scale_long(const ScaleTickArgs &a, const ScaleTickArgs *tpl, int32_t ntiles, bool slice,
-                             hipStream_t st) {
+                             bool shared_lists, hipStream_t st) {
     if (ntiles < 1) return hipErrorInvalidValue;
     const size_t lds = scale_lds_bytes(a.stride, slice, a.ev.buf != nullptr) + size_t(a.lds_pad);
     const dim3 grid(64), block(kScaleBlock);
     const int v = (slice ? 4 : 0) | (a.tfail > 0 ? 2 : 0) | (a.swim > 0 ? 1 : 0);
+    const int32_t sh = shared_lists ? 1 : 0;
     switch (v) {
-        case 0: hipLaunchKernelGGL((scale_long_kernel<false, false, false>), grid, block, lds, st, a, tpl, ntiles); break;
-        case 1: hipLaunchKernelGGL((scale_long_kernel<false, false, true>), grid, block, lds, st, a, tpl, ntiles); break;
-        case 2: hipLaunchKernelGGL((scale_long_kernel<false, true, false>), grid, block, lds, st, a, tpl, ntiles); break;
-        case 3: hipLaunchKernelGGL((scale_long_kernel<false, true, true>), grid, block, lds, st, a, tpl, ntiles); break;
-        case 4: hipLaunchKernelGGL((scale_long_kernel<true, false, false>), grid, block, lds, st, a, tpl, ntiles); break;
-        case 5: hipLaunchKernelGGL((scale_long_kernel<true, false, true>), grid, block, lds, st, a, tpl, ntiles); break;
-        case 6: hipLaunchKernelGGL((scale_long_kernel<true, true, false>), grid, block, lds, st, a, tpl, ntiles); break;
-        default: hipLaunchKernelGGL((scale_long_kernel<true, true, true>), grid, block, lds, st, a, tpl, ntiles); break;
+        case 0: hipLaunchKernelGGL((scale_long_kernel<false, false, false>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        case 1: hipLaunchKernelGGL((scale_long_kernel<false, false, true>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        case 2: hipLaunchKernelGGL((scale_long_kernel<false, true, false>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        case 3: hipLaunchKernelGGL((scale_long_kernel<false, true, true>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        case 4: hipLaunchKernelGGL((scale_long_kernel<true, false, false>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        case 5: hipLaunchKernelGGL((scale_long_kernel<true, false, true>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        case 6: hipLaunchKernelGGL((scale_long_kernel<true, true, false>), grid, block, lds, st, a, tpl, ntiles, sh); break;
+        default: hipLaunchKernelGGL((scale_long_kernel<true, true, true>), grid, block, lds, st, a, tpl, ntiles, sh); break;
     }
     return hipGetLastError();
 }

@@ -92,7 +92,25 @@ struct ScaleTickArgs {
     int32_t *cnt_sub;            // [stride / W][n] member counts per sub-slab (sweep_count_kernel
                                  // sums them into cnt_cur)
     int32_t *mid_list;           // as long_list, for the rows with sweep_seg < k <= kMaxSegment
+    int32_t appends;             // 1: this tile's sweep items append to long_list / mid_list (the
+                                 // CSR's owner).  The sweep reads its args from the tile table,
+                                 // where every tile holds the owner's lists (the long kernel
+                                 // reads them), so a null list cannot say it there
 };
+
+// What a tick changes in a tile's args beyond the tick parity: the tile table (ScaleTickArgs per
+// tile and parity, made once by the host) holds everything else, and tile_args (scale_row.hpp)
+// patches these in.  A new per-tick args field joins this struct and that one function.
+// A new POINTER field of ScaleTickArgs must join tile_args' to_global list as well: a pointer read
+// from the table is generic until it is cast there, the sweep would address it with flat_*
+// instructions, and that form measured +0.25 ms per tick at config 3 with nothing failing
+// (DESIGN.md "One launch for every tile"; check: 0 flat_ instructions in scale_sweep_kernel).
+struct ScaleTickVals {
+    int32_t tick, drop_pct, drop_prev;
+};
+__host__ __device__ inline ScaleTickVals tick_vals(const ScaleTickArgs &a) {
+    return {a.tick, a.drop_pct, a.drop_prev};
+}
 
 __host__ __device__ inline unsigned long long event_record(uint32_t kind, uint32_t t, uint32_t r,
                                                            uint32_t x) {
@@ -127,15 +145,22 @@ __device__ inline void wave_append_events(unsigned long long *buf, unsigned long
 
 // merge: 0 = per-entry scalar form, 1 = packed 16-bit form (v_pk_* / v_bfi_b32)
 hipError_t launch_scale_init(const ScaleTickArgs &a, bool slice, hipStream_t st);
-// a.sweep != 0 (slice form, packed merge, plain protocol): the sub-slab sweep
+// one workgroup per row of one tile
 hipError_t launch_scale_tick(const ScaleTickArgs &a, bool slice, int merge, hipStream_t st);
+// The tile table (device): tpl[2 * g + parity] = local tile g's args at tick parity, dig at tick
+// 0, every tile holding its CSR owner's deferred-row lists.
+// The sub-slab sweep (a.sweep != 0: slice form, packed merge, plain protocol) of every local tile
+// in one launch: tiles[0 .. ntiles) = the tiles' args of this tick (host; checked here: the
+// tiles must agree in rows and stride), tpl = the tile table the kernel reads them from
+hipError_t launch_scale_sweep(const ScaleTickArgs *tiles, int32_t ntiles, const ScaleTickArgs *tpl,
+                              hipStream_t st);
 // after a sweep launch: cnt_cur of `tiles` tiles (a = the first one's args; their cnt_sub and
 // cnt_cur lie one after the other) from the per-sub-slab counts
 hipError_t launch_sweep_counts(const ScaleTickArgs &a, int32_t tiles, hipStream_t st);
-// the rows every tick-kernel launch of this tick deferred (k > kMaxSegment): tpl[2 * g + parity]
-// = local tile g's args at tick parity (dig at tick 0); a = tile 0's args of this tick
+// the rows every tick-kernel launch of this tick deferred (k > kMaxSegment); a = tile 0's args of
+// this tick; shared_lists: every tile's lists are tile 0's (one CSR), so their counts are read once
 hipError_t launch_scale_long(const ScaleTickArgs &a, const ScaleTickArgs *tpl, int32_t ntiles, bool slice,
-                             hipStream_t st);
+                             bool shared_lists, hipStream_t st);
 
 // Column mode, after the all-gather of every shard's per-row slice counts:
 //   resolve: per sender, Philox rank-select over the global order of its members; the

@@ -308,6 +308,32 @@ __device__ __forceinline__ void ev_flush(unsigned long long *ev_buf, const uint3
     __builtin_amdgcn_wave_barrier();
 }
 
+// Tile g's args of this tick from the tile table (scale_kernels.hpp): its template of the tick's
+// parity with the tick's own values patched in.  The one list of per-tick fields on the device:
+// the sweep and the long kernel both build their args here.
+// A pointer read from memory is a generic one to the compiler, unlike a kernel argument, and
+// generic accesses (flat_*) count on both memory counters: every wait for an LDS permute would
+// also wait for the row vectors in flight.  The table's pointers are all device memory.
+template <typename T>
+__device__ __forceinline__ void to_global(T *&p) {
+    p = (T *)(__attribute__((address_space(1))) T *)(uintptr_t)p;     // (through an integer: a cast pair folds away)
+}
+
+__device__ __forceinline__ ScaleTickArgs tile_args(const ScaleTickArgs *tpl, int32_t g, const ScaleTickVals &tv) {
+    ScaleTickArgs a = tpl[2 * g + (tv.tick & 1)];
+    a.tick = tv.tick;
+    a.drop_pct = tv.drop_pct;
+    a.drop_prev = tv.drop_prev;
+    a.dig += size_t(tv.tick) * kDigSlots * kDigFields;
+    to_global(a.prev); to_global(a.cur); to_global(a.remote); to_global(a.fail_tick);
+    to_global(a.start_tick); to_global(a.intro); to_global(a.intro_cnt); to_global(a.own_hb);
+    to_global(a.cnt_prev); to_global(a.cnt_cur); to_global(a.off); to_global(a.csr_src);
+    to_global(a.csr_slot); to_global(a.out_dst); to_global(a.deg); to_global(a.ping);
+    to_global(a.bitmap); to_global(a.dig); to_global(a.ev.buf); to_global(a.ev.count);
+    to_global(a.err); to_global(a.long_list); to_global(a.cnt_sub); to_global(a.mid_list);
+    return a;
+}
+
 // Append row lr to a deferred-row list (list[0]: its length), by one lane of the CSR's owner
 __device__ __forceinline__ void defer_row(int32_t *list, int32_t lr) {
     if (list) list[1 + atomicAdd(&list[0], 1)] = lr;

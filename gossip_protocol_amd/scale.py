@@ -94,6 +94,12 @@ class ScaleEngine(ProbeMethods):
               "gsp_scale_layout")
         return g.value, r.value, s.value
 
+    def sweep(self):
+        """(sub-slab width of the tile sweep, 0 = one workgroup per row; deferral bound)."""
+        w, k = ctypes.c_int32(), ctypes.c_int32()
+        check(lib().gsp_scale_sweep(self._h, ctypes.byref(w), ctypes.byref(k)), "gsp_scale_sweep")
+        return w.value, k.value
+
     def set_merge(self, packed):
         check(lib().gsp_scale_set_merge(self._h, int(packed)), "gsp_scale_set_merge")
 

@@ -445,6 +445,9 @@ int gsp_scale_create_group_layout(const gsp_scale_params *p, int device, int32_t
 /* shards of the job, first shard index held by this engine, columns per shard (row layout:
  * the full row stride) */
 int gsp_scale_layout(gsp_scale *s, int32_t *shards, int32_t *rank, int64_t *stride);
+/* the tick form fixed at create: *width = columns per sub-slab of the tile sweep (0: one
+ * workgroup per row), *seg = messages a row may have before the sweep defers it */
+int gsp_scale_sweep(gsp_scale *s, int32_t *width, int32_t *seg);
 int gsp_scale_destroy(gsp_scale *s);
 /* Advance `ticks` ticks on the device (no host synchronisation inside). */
 int gsp_scale_step(gsp_scale *s, int32_t ticks);
